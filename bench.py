@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmarks of the SENSE hot path on MI355X (BASELINE.json metric and configs).
 
-    python bench.py --gpus N --steps K --warmup W [--config {1,2,3,4,5}]
+    python bench.py --gpus N --steps K --warmup W [--config {1,2,3,4,5}] [--dump-outputs DIR]
 
 Default (`--config 4`, BASELINE.json's metric): one "step" is one evaluation y = A^H A x of the composed
 non-Cartesian SENSE normal operator (the reference's `-O3` tree S' -> FFT -> G' -> G'^H -> IFFT -> S'^H, with S' and
@@ -34,6 +34,11 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   eval_traffic_*   : bytes the whole evaluation really moves (PMC summary) and the fraction of the 8 TB/s peak that
                      is; `reference_model_*`: the same evaluation priced with the reference's leaf-by-leaf model
                       -- a speed-up measure, NOT a roofline fraction (fusion removed those bytes)
+
+`--dump-outputs DIR` writes, after the timed steps, what the selected config's timed path computed in its last step as
+DIR/<name>.npy (float32, a trailing (re, im) axis; see dump_outputs): the inputs are seeded, so two builds run with the same
+arguments can be compared output for output -- with a tolerance: two runs of one build have been seen to differ by about 1e-7
+(relative 2-norm of the headline's output), not bit for bit.
 """
 import argparse
 import json
@@ -152,7 +157,7 @@ def pmc_stale(pmc, symbols=()):
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps of the selected config (each extra measurement times its own few)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", type=int, default=4, choices=[1, 2, 3, 4, 5])
     ap.add_argument("--image", default="", help="image edge, or X,Y,Z for a non-cubic image (config 4: e.g. 480,208,308 --osf 1.3333 is the "
@@ -183,7 +188,11 @@ def parse():
     ap.add_argument("--batch", type=int, default=16, help="config 2: number of volumes")
     ap.add_argument("--ncol", type=int, default=64, help="config 3: panel columns")
     ap.add_argument("--no-extras", action="store_true", help="only the selected config: --no-config5 --no-leaf-configs (profiling runs)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the selected config's timed path "
+                    "computed in its last step as DIR/<name>.npy (float32 (re, im) pairs; a seeded sample of rows when larger than the budget)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.no_extras:
         args.no_config5 = args.no_leaf_configs = args.no_dense = True
     dims = [int(v) for v in str(args.image).split(",") if v.strip()] if args.image else []
@@ -213,6 +222,36 @@ def claim_stdout():
 def log(*a):
     if RANK == 0:
         print("[bench]", *a, file=sys.stderr, flush=True)
+
+
+DUMP_BUDGET = 48 << 20      # bytes of data --dump-outputs writes in all (64 MB at most, the .npy headers included)
+DUMP_SEED = 12345
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: device arrays [(name, dndarray)] -> dirpath/<name>.npy on rank 0, float32 of shape (rows, columns, 2) with
+    (re, im) last; rows = the array flattened in F order over all axes but its last, columns = its last axis.  An array larger
+    than its share of DUMP_BUDGET keeps the same seeded sample of rows (sorted) in every column: the sample depends on the shape
+    and DUMP_SEED alone, so two builds given the same arguments write comparable files.  Copied one column at a time."""
+    import numpy as np
+    if not dirpath or RANK != 0:
+        return
+    os.makedirs(dirpath, exist_ok=True)
+    share = DUMP_BUDGET // max(1, len(arrays))
+    for name, a in arrays:
+        shape = tuple(int(n) for n in a.shape)
+        ncol = shape[-1] if len(shape) > 1 else 1
+        nrow = int(np.prod(shape)) // ncol
+        take = max(1, min(nrow, share // (8 * ncol)))
+        rows = None if take == nrow else np.sort(np.random.default_rng(DUMP_SEED).choice(nrow, take, replace=False))
+        out = np.empty((take, ncol, 2), dtype=np.float32)
+        for j in range(ncol):
+            col = (a if ncol == 1 else a[(slice(None),) * (len(shape) - 1) + (slice(j, j + 1),)]).to_host().ravel(order='F')
+            col = col if rows is None else col[rows]
+            out[:, j, 0], out[:, j, 1] = col.real, col.imag
+        np.save(os.path.join(dirpath, name + ".npy"), out)
+        log("dump: %s %s -> %s.npy %s%s" % (name, shape, name, out.shape, "" if rows is None else
+                                            " (%d of %d rows, seeded sample)" % (take, nrow)))
 
 
 def timed_steps(B, comm, fn, steps, warmup):
@@ -398,7 +437,7 @@ def sense_problem(cfg, img, C, osf=0.0, dims=None, spokes_scale=1.0, width=2.0):
                                   oversamp=1.6, seed=5, lazy_maps=True)
 
 
-def run_sense(args, cfg, B, comm, world, rank, steps, warmup, want_cpu, quiet=False, want_parity=False):
+def run_sense(args, cfg, B, comm, world, rank, steps, warmup, want_cpu, quiet=False, want_parity=False, dump=None):
     import numpy as np
     from indigo_amd.dist import ShardedNormalOperator, coil_range
     from indigo_amd.sense import normal_operator
@@ -464,6 +503,7 @@ def run_sense(args, cfg, B, comm, world, rank, steps, warmup, want_cpu, quiet=Fa
         setup_s, ref_bytes_rank / 1e9, {k: round(v['nbytes'] / 1e9, 2) for k, v in ev.items()}))
 
     elapsed, prof = timed_steps(B, comm, lambda: AHA.eval(y, x), steps, warmup)
+    dump_outputs(dump, [("AHA_x", y)])
     ms_per_step = elapsed / steps * 1e3
     value = steps / elapsed
 
@@ -538,6 +578,9 @@ def run_sense(args, cfg, B, comm, world, rank, steps, warmup, want_cpu, quiet=Fa
     if traffic_bytes is None:
         traffic_bytes, traffic_src = comp_bytes, "sum of the kernels' compulsory bytes (no PMC summary for this configuration)"
 
+    placement = [list(e) for e in getattr(B, "_placement_log", [])][-4:]
+    for nbytes, cands, kept in placement:
+        log("placement: %d bytes, window kept at %.4f ms; candidates' probe times %s" % (nbytes, kept, cands))
     out = {
         "ms_per_step": ms_per_step, "value": value, "setup_s": round(setup_s, 2),
         "config": {"workload": "non-Cartesian SENSE A^H A, image %s, %d coils, grid %s (osf %.4g), radial T=%d, KB width %g; "
@@ -551,8 +594,9 @@ def run_sense(args, cfg, B, comm, world, rank, steps, warmup, want_cpu, quiet=Fa
                    "coil_chunk_widths": [lf['width'] for lf in leaves_z] or None, "spokes_scale": scale,
                    "support_table_kx_points_per_entry": (sup_tile if sup_tab is not None else None),
                    # large arrays are placed by probing: the best 1 GB window of an allocation 24 GB longer than the array (HipBackend.tuning[placement_window_gb / _allocs],
-                   # DESIGN.md 3.1): bytes, the candidates' probe times in ms, the one kept -- part of set-up, outside the timed region
-                   "placement": [list(e) for e in getattr(B, "_placement_log", [])][-4:] or None},
+                   # DESIGN.md 3.1): bytes and the probe time in ms of the window kept -- part of set-up, outside the timed region (the
+                   # candidates' probe times go to the log: they would make up a fifth of the result line)
+                   "placement": [[nbytes, kept] for nbytes, _, kept in placement] or None},
         "roofline": roofline,
         "eval_traffic_GB": traffic_bytes / 1e9,
         "eval_traffic_frac": traffic_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
@@ -651,7 +695,8 @@ def bench_sense(args, world, rank, local_rank):
     log("device:", B.device_name(), "world", world)
     cfg = args.config
     want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and not args.shard and cfg == 4
-    res = run_sense(args, cfg, B, comm, world, rank, args.steps, args.warmup, want_cpu, want_parity=(args.parity and world == 1 and not args.shard))
+    res = run_sense(args, cfg, B, comm, world, rank, args.steps, args.warmup, want_cpu, want_parity=(args.parity and world == 1 and not args.shard),
+                    dump=args.dump_outputs)
 
     import threading
     emit_lock = threading.Lock()
@@ -725,6 +770,7 @@ def bench_sense(args, world, rank, local_rank):
         for c, fn in ((2, bench_fft), (3, bench_spmm)):
             a2 = copy.copy(args)
             a2.config, a2.image, a2.steps, a2.warmup = c, 0, max(5, min(args.steps, 10)), min(args.warmup, 3)
+            a2.dump_outputs = ""
             try:
                 B._scratch = None
                 r = fn(a2, local_rank, B)
@@ -796,6 +842,7 @@ def bench_fft(args, local_rank, B=None):
     log("config 2: %s; plan: %s" % (shape, B.fft_describe(shape)))
     nbytes = x.nbytes
     elapsed, prof = timed_steps(B, None, lambda: B.fftn(yv, x), args.steps, args.warmup)
+    dump_outputs(args.dump_outputs, [("fftn_y", yv)])
     ms = elapsed / args.steps * 1e3
     tot_kernel_ms = sum(v['total_ms'] for v in prof.values()) / args.steps
     pmc, src = load_pmc(2) if n == 256 and batch == 16 else (None, None)
@@ -879,6 +926,7 @@ def bench_spmm(args, local_rank, B=None):
     elapsed, prof = timed_steps(B, None, lambda: S.eval(Y, X), args.steps, args.warmup)
     ms = elapsed / args.steps * 1e3
     a_elapsed, a_prof = timed_steps(B, None, lambda: S.eval(Z, Y, forward=False), args.steps, args.warmup)
+    dump_outputs(args.dump_outputs, [("csrmm_Y", Y), ("csrmm_adjoint_Z", Z)])
     a_ms = a_elapsed / args.steps * 1e3
     pmc, src = load_pmc(3) if n == 256 and ncol == 64 else (None, None)
     traffic = traffic_note = None
@@ -983,8 +1031,9 @@ def bench_spmm_example(args, local_rank):
     x = B.copy_array(xh)
     y = B.zero_array((10000, 8), np.dtype('complex64'))
     S.eval(y, x)
-    elapsed, prof = timed_steps(B, None, lambda: S.eval(y, x), max(args.steps, 50), args.warmup)
-    steps = max(args.steps, 50)
+    steps = args.steps
+    elapsed, prof = timed_steps(B, None, lambda: S.eval(y, x), steps, args.warmup)
+    dump_outputs(args.dump_outputs, [("spmm_y", y)])
     ms = elapsed / steps * 1e3
     O = NumpyBackend()
     So = O.SpMatrix(A)
