@@ -475,7 +475,8 @@ int  ig_interp3_fill_modulated(int64_t m, const int64_t* N, double width, const 
  *   word 3 tw       first tap (wrapped) on axis 0 | first tap on axis 1 << 16
  *   word 3 tw + 1   first tap on axis 2 | taps on axis 0 << 16 | taps on axis 1 << 20 | taps on axis 2 << 24
  * tw = 4 (kernel half-width <= 2), 6 (<= 3) or 8 (<= 4): 16 / 32 / 32 words.  sign_x / _y / _z: +-1 per grid cell of the
- * REFERENCE axes x, y, z (N[0] / N[1] / N[2] doubles) or NULL.  IG_ERR_UNSUPPORTED when a sample has more than tw taps on an axis.
+ * REFERENCE axes x, y, z (N[0] / N[1] / N[2] doubles) or NULL.  IG_ERR_UNSUPPORTED when a sample has more than tw taps on an axis,
+ * or none (a half-width below 1: the gridding kernels read the last tap of every axis).
  * Host memory.  The gridding kernels that compute their taps from these records: ig_grid_gather_sep, ig_grid_scatter_sep.   */
 int  ig_interp3_sep_words(int tw);
 int  ig_interp3_sep(int64_t m, const int64_t* N, double width, const double* table, int64_t ntable, const double* coord,

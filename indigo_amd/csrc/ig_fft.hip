@@ -1043,6 +1043,15 @@ void factor_generic(int64_t n, std::vector<int64_t>& out) {
     if (m > 1) out.push_back(m);
 }
 
+// the largest prime factor of n (factor_generic groups the twos into radices 8 and 4: its largest entry is no prime factor)
+int64_t largest_prime_factor(int64_t n) {
+    int64_t big = 1, m = n;
+    while (m > 1 && m % 2 == 0) { big = 2; m /= 2; }
+    for (int64_t p = 3; p * p <= m; p += 2)
+        while (m % p == 0) { big = p; m /= p; }
+    return m > 1 ? m : big;
+}
+
 }  // namespace
 
 struct ig_fft {
@@ -2052,10 +2061,7 @@ int ig_fft_support_words(int64_t n, int* zw_in, int* zw_out) {
     if (n == 256 || n == 512) { *zw_in = *zw_out = 16; return IG_OK; }
     if (abd_supported(n) && ab_split(n, A, B)) { *zw_in = B; *zw_out = A; return IG_OK; }
     {   // a chirp-z axis (a prime factor above 7) over an A x B length: B words on both sides
-        std::vector<int64_t> f;
-        factor_generic(n, f);
-        int64_t big = 1;
-        for (int64_t r : f) big = std::max(big, r);
+        const int64_t big = largest_prime_factor(n);
         if (big > 7 && n >= 32 && chirp_ab_length(n, A, B) && n <= 32 * (int64_t)B) { *zw_in = *zw_out = B; return IG_OK; }
     }
     return ig_fail(nullptr, IG_ERR_UNSUPPORTED, "ig_fft_support_words: no zero-pad-aware z pass for an axis of %lld points", (long long)n);
@@ -2067,11 +2073,9 @@ int ig_fft_padded_axis_kind(int64_t n, int* kind) {
     *kind = 0;
     if (n == 256 || n == 512) { *kind = 3; return IG_OK; }
     if (abd_supported(n)) { *kind = 4; return IG_OK; }
-    // chirp-z: a length with a prime factor above 7 whose 2 n - 1 is covered by an A x B length
-    std::vector<int64_t> f;
-    factor_generic(n, f);
-    int64_t big = 1;
-    for (int64_t r : f) big = std::max(big, r);
+    // chirp-z: a length with a prime factor above 7 whose 2 n - 1 is covered by an A x B length (64 or 96 are not: the plan transforms
+    // them with the LDS kernel, which the zero-pad-aware passes do not take)
+    const int64_t big = largest_prime_factor(n);
     if (big > 7 && n >= 32)
         for (int64_t c = 2 * n - 1; c <= 1024; ++c) if (ab_split(c, A, B)) { *kind = 5; break; }
     return IG_OK;

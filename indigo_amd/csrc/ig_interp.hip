@@ -216,6 +216,9 @@ extern "C" int ig_interp3_sep(int64_t m, const int64_t* N, double width, const d
                 const double pos = (double)n * c[d][i] + (double)(n / 2);
                 const Taps t = taps_of(pos, width);
                 if (t.count > tw) bad = 1;
+                // (below half-width 1 an axis can have no tap at all: the gridding kernels read the last tap of every axis, so such a
+                // sample has no record -- the caller keeps the stored-tap formats, where it is an empty row)
+                if (t.count < 1) bad = 2;
                 const int64_t cnt = t.count > tw ? tw : t.count;
                 first[a] = (uint32_t)wrap(t.start, n);
                 count[a] = (uint32_t)cnt;
@@ -232,6 +235,7 @@ extern "C" int ig_interp3_sep(int64_t m, const int64_t* N, double width, const d
             r[3 * tw + 1] = first[2] | (count[0] << 16) | (count[1] << 20) | (count[2] << 24);
         }
     });
+    if (bad == 2) return ig_fail(nullptr, IG_ERR_UNSUPPORTED, "ig_interp3_sep: a sample has no tap on an axis (kernel half-width %g)", width);
     if (bad) return ig_fail(nullptr, IG_ERR_UNSUPPORTED, "ig_interp3_sep: a sample has more than tw = %d taps on an axis (kernel half-width %g)", tw, width);
     return IG_OK;
 }

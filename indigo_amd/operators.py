@@ -632,6 +632,12 @@ class Kron(BinaryOperator):
     def _eval(self, y, x, alpha=1, beta=0, forward=True, left=True):
         L, R = self._children
         if isinstance(L, Eye):
+            if x.shape[1] > 1 and getattr(R, '_grid_interleaved', False):
+                # a coil-interleaved grid (ZpadFFT layout 2) per column: the c blocks of ONE column are the c columns of its own
+                # row-major panel, so the columns cannot be stacked side by side as one wider panel -- one product per column
+                for j in range(x.shape[1]):
+                    R.eval(y[:, j:j + 1], x[:, j:j + 1], alpha=alpha, beta=beta, forward=forward, left=left)
+                return
             # I_c (x) B: the c blocks become c panel columns; R.eval does the reshape
             R.eval(y, x, alpha=alpha, beta=beta, forward=forward, left=left)
         else:

@@ -112,9 +112,10 @@ class SenseProblem(object):
         """G' = interp * mod * (1/sqrt(P)) as a complex64 CSR (T x P).
         layout=1 indexes the grid columns in (x, z, y) memory order (see operators.ZpadFFT).
         phases: per-axis phase arrays to use INSTEAD of the centred transform's modulation -- a leaf whose transform carries the
-        modulation of an odd axis itself (HipBackend.fold_axis_shifts) asks for the matrix without it; not cached under `layout`"""
+        modulation of an odd axis itself (HipBackend.fold_axis_shifts) asks for the matrix without it; cached under `layout` and the
+        phases themselves (the backend's tuning decides which phases a leaf asks for, and may change between two builds)"""
         if phases is not None:
-            key = ('folded', layout)
+            key = ('folded', layout, _phases_key(phases))
             if key not in self._interp_cache:
                 P = int(np.prod(self.oN))
                 scale = np.float32(1.0) / np.sqrt(np.float32(P))
@@ -139,7 +140,7 @@ class SenseProblem(object):
         """G' in separable form (indigo_amd.interp.interp_sep_records: one record per sample -- first tap, tap counts and per-axis
         weights with the modulation's sign folded in) for the grid order of `layout`, or None when the grid's modulation is no sign
         per axis (odd axes -- unless the leaf's transform carries their modulation: `phases`, as for fused_interp)"""
-        key = ('sep', layout) if phases is None else ('sep-folded', layout)
+        key = ('sep', layout) if phases is None else ('sep-folded', layout, _phases_key(phases))
         if key not in self._interp_cache:
             P = int(np.prod(self.oN))
             scale = np.float32(1.0) / np.sqrt(np.float32(P))
@@ -345,6 +346,17 @@ class SenseProblem(object):
 def backend_mod(ft_shape):
     from indigo_amd.backends.backend import Backend
     return Backend.fftc_mod(ft_shape, _C64)
+
+
+def _phases_key(phases):
+    """digest of per-axis phase arrays: part of the cache key of every gridding matrix built from them"""
+    import hashlib
+    h = hashlib.sha1()
+    for ph in phases:
+        a = np.ascontiguousarray(ph, dtype=np.float64)
+        h.update(np.int64(a.size).tobytes())
+        h.update(a.tobytes())
+    return h.hexdigest()
 
 
 def _mod_axis_phases(ft_shape):
