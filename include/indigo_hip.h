@@ -175,6 +175,14 @@ int  ig_csum_cols(ig_ctx* ctx, int64_t rows, int64_t ncols, const void* X, int64
 /* the same sum over a row-major (coil-interleaved) panel: y[k] = beta*y[k] + alpha * sum_j X_il[k*ncols + j] */
 int  ig_csum_il(ig_ctx* ctx, int64_t rows, int64_t ncols, const void* X_il,
                 float alpha_re, float alpha_im, float beta_re, float beta_im, void* y);
+/* y[:, j] = beta*y[:, j] + alpha * permute(x[:, j]) for ncols columns (leading dims ldx, ldy >= n0*n1*n2): column j of x is
+ * an F-ordered n0 x n1 x n2 volume, and output axis a is input axis perm[a] -- numpy
+ * x.reshape((n0, n1, n2), order='F').transpose(perm).ravel(order='F').  The relabelling of the image axes that lets the
+ * fused SENSE leaf run a grid whose x axis it has no zero-pad-aware pass for on a permuted grid (operators.AxisPermute).
+ * x == y, a perm that is not one of (0, 1, 2), or a leading dimension below the volume: IG_ERR_ARG.                       */
+int  ig_permute3_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, const int perm[3], int64_t ncols,
+                     const void* x, int64_t ldx, float alpha_re, float alpha_im, float beta_re, float beta_im,
+                     void* y, int64_t ldy);
 
 /* ------------------------------------------------------------------------
  * CSR x dense-panel SpMM.  Replaces Backend.ccsrmm

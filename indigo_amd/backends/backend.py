@@ -378,6 +378,11 @@ class Backend(object):
     def Crop(self, M, N, dtype=_C64, **kwargs):
         return self.Zpad(N, M, dtype=dtype, **kwargs).H
 
+    def AxisPermute(self, dims, perm, **kwargs):
+        """the image -> image relabelling of the axes of an F-ordered `dims` volume: output axis a is input axis perm[a]
+        (see operators.AxisPermute)"""
+        return op.AxisPermute(self, dims, perm, **kwargs)
+
     def Interp(self, N, coord, width, table, dtype=_C64, **kwargs):
         """gridding / interpolation matrix (npts x prod N) from a k-space trajectory"""
         assert len(N) == 3
@@ -478,6 +483,22 @@ class Backend(object):
     def sum_columns(self, y, X, alpha=1, beta=0, interleaved=False):
         """y = beta*y + alpha * sum_j X[:, j]  (interleaved: X's memory holds element (i, j) at i*ncols + j)"""
         raise NotImplementedError()
+
+    def permute3(self, y, x, dims, perm, alpha=1, beta=0):
+        """y[:, j] = beta*y[:, j] + alpha * permute(x[:, j]) for every column j: a column is an F-ordered `dims` volume, output axis
+        a is input axis perm[a] (numpy transpose(perm) in F order).  beta == 0: y is not read.  This host form goes through
+        to_host / copy_from, so that every backend has it; device backends override it."""
+        dims, perm = tuple(int(n) for n in dims), tuple(int(p) for p in perm)
+        assert len(dims) == 3 and sorted(perm) == [0, 1, 2], (dims, perm)
+        n = int(np.prod(dims))
+        assert x.size % n == 0 and x.size == y.size, (x.shape, y.shape, dims)
+        ncols = x.size // n
+        xh = x.to_host().reshape(dims + (ncols,), order='F')
+        out = np.asfortranarray(xh.transpose(perm + (3,))).reshape((n, ncols), order='F')
+        out = (out * np.complex64(alpha)).astype(_C64) if alpha != 1 else out.astype(_C64)
+        if beta != 0:
+            out = (y.to_host().reshape((n, ncols), order='F') * np.complex64(beta) + out).astype(_C64)
+        y.copy_from(np.asfortranarray(out.reshape(y.shape, order='F')))
 
     def supports_padded_fft(self, grid, ncoils=None):
         """whether `fft_padded` / `ifft_cropped[_sum]` exist for this oversampled grid (and, if given, this many coils)"""

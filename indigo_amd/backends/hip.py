@@ -848,6 +848,19 @@ class HipBackend(Backend):
         self._check(self._L.ig_csum_cols(self._ctx, X.shape[0], X.shape[1], ctypes.c_void_p(X._arr), X._leading_dim,
                                          ar, ai, br, bi, ctypes.c_void_p(y._arr)), "ig_csum_cols")
 
+    def permute3(self, y, x, dims, perm, alpha=1, beta=0):
+        """Backend.permute3 on the device (ig_permute3_c64): panels of any column count with their leading dimensions"""
+        assert x.dtype == _C64 and y.dtype == _C64, "only complex64 is supported"
+        n0, n1, n2 = (int(n) for n in dims)
+        n = n0 * n1 * n2
+        assert x.shape[0] == n and y.shape[0] == n and x.size == y.size, (x.shape, y.shape, dims)
+        ncols = x.shape[1] if x.ndim == 2 else 1
+        p = (ctypes.c_int * 3)(*(int(v) for v in perm))
+        ar, ai = _cplx(alpha)
+        br, bi = _cplx(beta)
+        self._check(self._L.ig_permute3_c64(self._ctx, n0, n1, n2, p, ncols, ctypes.c_void_p(x._arr), x._leading_dim,
+                                            ar, ai, br, bi, ctypes.c_void_p(y._arr), y._leading_dim), "ig_permute3_c64")
+
     def fftn(self, y, x):
         self._fft(y, x, -1)
 

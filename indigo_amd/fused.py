@@ -16,17 +16,39 @@ import scipy.sparse as spp
 _C64 = np.dtype('complex64')
 
 
-def permute_grid_columns(G, oN):
-    """Renumber the columns of a gridding matrix from the (x, y, z) grid order to (x, z, y); sorted CSR."""
-    n0, n1, n2 = (int(n) for n in oN)
+def permute_grid_columns(G, oN, order=(0, 2, 1)):
+    """Renumber the columns of a gridding matrix from the (x, y, z) grid order of an oN grid to the F order of the grid with its
+    axes taken in `order` (memory axis a = grid axis order[a]): the default (0, 2, 1) is the (x, z, y) order of layout 1; sorted CSR.
+    The result shares G's data array, which the sort reorders: hand over a matrix of your own (callers pass a fresh astype copy)."""
+    n = [int(v) for v in oN]
+    o = [int(a) for a in order]
     G = G.tocsr()
     idx = G.indices.astype(np.int64)
-    kx = idx % n0
-    ky = (idx // n0) % n1
-    kz = idx // (n0 * n1)
-    out = spp.csr_matrix((G.data, (kx + n0 * (kz + n2 * ky)).astype(np.int32), G.indptr), shape=G.shape)
+    k = (idx % n[0], (idx // n[0]) % n[1], idx // (n[0] * n[1]))
+    out = spp.csr_matrix((G.data, (k[o[0]] + n[o[0]] * (k[o[1]] + n[o[1]] * k[o[2]])).astype(np.int32), G.indptr), shape=G.shape)
     out.sort_indices()
     return out
+
+
+def image_permutation(backend, grid, ncoils=None):
+    """The relabelling of the image axes under which the fused leaf runs a grid it refuses, or None.
+
+    The NUFFT is separable: permuting the image axes permutes the grid axes, the trajectory rows, the roll-off, the maps and
+    the modulation's per-axis phases, and nothing else (the k-space sample order is untouched).  So a grid whose x axis has no
+    zero-pad-aware pass -- int(N * osf) of the reference's sizing gives chirp-z x axes for ordinary image sizes: 52 -> 69,
+    208 -> 277 -- runs as  A = A_perm * AxisPermute(N, perm)  with A_perm the leaf on the grid grid[perm].
+    None where the backend takes the grid as it is (its route does not change) or under no permutation (69^3).  Else, among
+    the accepted permutations: one that puts a multiple of 16 on x first (the support table and the brick formats need it),
+    then a swap before a 3-cycle, then the lowest in lexicographic order."""
+    grid = tuple(int(v) for v in grid)
+    if len(grid) != 3 or backend.supports_padded_fft(grid, ncoils):
+        return None
+    import itertools
+    ok = [p for p in itertools.permutations(range(3))
+          if p != (0, 1, 2) and backend.supports_padded_fft(tuple(grid[a] for a in p), ncoils)]
+    if not ok:
+        return None
+    return min(ok, key=lambda p: (grid[p[0]] % 16 != 0, sum(p[a] != a for a in range(3)) != 2, p))
 
 
 def touched_columns(G):

@@ -484,6 +484,33 @@ class ZpadFFT(MatrixFreeOperator):
         return (N * C * 8 + 255) // 256 * 256 + self._ws_bytes()
 
 
+class AxisPermute(MatrixFreeOperator):
+    """Relabelling of the axes of an F-ordered image volume of shape `dims`: output axis a is input axis perm[a], i.e.
+    y = x.reshape(dims, order='F').transpose(perm).ravel(order='F');  the adjoint is the inverse permutation.  Pure data
+    movement (backend.permute3), shape (N, N).
+
+    What lets the fused SENSE leaf run a grid it refuses: the NUFFT is separable, so relabelling the image axes relabels
+    the grid axes, the trajectory rows, the roll-off, the maps and the modulation phases and nothing else --
+    A = A_perm * AxisPermute(N, perm), with A_perm the leaf on the permuted problem (indigo_amd.fused.image_permutation)."""
+
+    def __init__(self, backend, dims, perm, **kwargs):
+        self._dims = tuple(int(n) for n in dims)
+        self._perm = tuple(int(p) for p in perm)
+        assert len(self._dims) == 3 and sorted(self._perm) == [0, 1, 2], (dims, perm)
+        self._inv = tuple(int(a) for a in np.argsort(self._perm))
+        n = int(np.prod(self._dims))
+        kwargs.setdefault('name', 'permute%s' % (self._perm,))
+        super().__init__(backend, shape=(n, n), **kwargs)
+
+    def _eval(self, y, x, alpha=1, beta=0, forward=True, left=True):
+        dims, perm = (self._dims, self._perm) if forward else (tuple(self._dims[p] for p in self._perm), self._inv)
+        trace = getattr(self._backend, 'trace', None)
+        if trace is not None:
+            trace.add('permute', nbytes=x.nbytes + y.nbytes * (1 if beta == 0 else 2), nflops=0, shape=x.shape,
+                      forward=forward, name=self._name)
+        self._backend.permute3(y, x, dims, perm, alpha=alpha, beta=beta)
+
+
 class Eye(MatrixFreeOperator):
     def __init__(self, backend, n, **kwargs):
         super().__init__(backend, shape=(n, n), **kwargs)

@@ -304,6 +304,18 @@ class SenseProblem(object):
         and stays the size the kernels were tuned on (indigo_amd.fused.assemble)."""
         coils = list(range(self.C) if coils is None else coils)
         Cn = len(coils)
+        perm = fused.image_permutation(backend, self.oN, Cn)
+        if perm is not None:
+            # a grid the leaf refuses but takes with its axes relabelled: the leaf on the permuted problem after a permutation of
+            # the image (A = A_perm * P_perm; its adjoint permutes back)
+            q = self.permuted(perm)
+            A = q.build_zpadfft(backend, coils=coils, layout=layout, support=support, reorder=reorder, chunk=chunk)
+            for attr in ('last_support_table', 'last_support_zw', 'last_support_fine'):
+                setattr(self, attr, getattr(q, attr, None))
+            out = A * backend.AxisPermute(self.N, perm)
+            out._name = A._name
+            out._image_permutation = perm
+            return out
         single_ok = getattr(backend, 'supports_single_coil_layout', lambda g: True)(self.oN)
         tuning = getattr(backend, 'tuning', {})
         layout, chunks = fused.choose_layout(Cn, chunk, layout, single_ok, tuning.get('chunk_cost'), tuning.get('chunk_pad', True))
@@ -331,6 +343,22 @@ class SenseProblem(object):
                            sep=self.fused_interp_sep(1, phases=folded) if (layout == 2 and order is None) else None, kshift=kshift)
         self.last_support_fine = getattr(A, '_support_fine', None)       # (table, tile) when the tree took a finer table
         return A
+
+    def permuted(self, perm):
+        """the same problem with its image axes relabelled (axis a of the new one is axis perm[a] of this one): N, the grid, the
+        trajectory rows and the maps permuted (array maps as a transposed view, lazy maps wrapped).  Its gridding matrices live in
+        this problem's cache (they do not depend on the maps) until drop_cache()"""
+        perm = tuple(int(a) for a in perm)
+        N = tuple(self.N[a] for a in perm)
+        if callable(self.maps):
+            src = self.maps
+            maps = (lambda c: src(c).transpose(perm))
+        else:
+            maps = self.maps.transpose(perm + (3,))
+        q = SenseProblem(N, self.coord[list(perm)], maps, width=self.width, ntable=self.ntable, oversamp=self.oversamp, ncoils=self.C)
+        assert q.oN == tuple(self.oN[a] for a in perm)
+        q._interp_cache = self._interp_cache.setdefault(('permuted', perm), {})
+        return q
 
     def build_fused(self, backend, coils=None):
         coils = list(range(self.C) if coils is None else coils)

@@ -297,8 +297,15 @@ class FuseZpadFFT(Transform):
             return node
         C = F.left.shape[0]
         grid = F.right._ft_shape
-        if L.left.shape[0] != C or len(grid) != 3 or not b.supports_padded_fft(grid, C):
+        if L.left.shape[0] != C or len(grid) != 3:
             return node
+        # a grid the leaf refuses may still run with the image axes relabelled (fused.image_permutation): the leaf is then assembled
+        # on the permuted grid and follows an AxisPermute of the image
+        perm = None
+        if not b.supports_padded_fft(grid, C):
+            perm = fused.image_permutation(b, grid, C)
+            if perm is None:
+                return node
         from indigo_amd.structured import InterpS, SelectS
         P = int(np.prod(grid))
         if isinstance(X, Adjoint) and isinstance(X.child, SpMatrix):
@@ -332,12 +339,19 @@ class FuseZpadFFT(Transform):
             log.warning("FuseZpadFFT: %s is not a zero-pad * diagonal factor; the tree keeps the unfused -O3 leaves (S' csrmm + dense FFT)", X._name)
             return node
         lo, box, w = dec
+        gs = _struct(L.right)
+        grid0 = tuple(grid)          # (the grid the recipe's G' numbers its columns on)
+        if perm is not None:
+            image = tuple(box)
+            lo, box = tuple(lo[a] for a in perm), tuple(box[a] for a in perm)
+            w = w.transpose(tuple(perm) + (3,))
+            gs = _permuted_interp(b, gs, grid0, perm)
+            grid = tuple(grid0[a] for a in perm)
         tuning = getattr(b, 'tuning', {})
         layout, chunks = fused.choose_layout(C, self.chunk, None, getattr(b, 'supports_single_coil_layout', lambda g: True)(grid),
                                              tuning.get('chunk_cost'), tuning.get('chunk_pad', True))
         # G' = interp * mod * scale: where the factories' description survived the recipe and the backend has a native builder, the
         # matrix is built directly in the leaf's grid order (ig_interp3_fill_modulated); else from the scipy product, renumbered
-        gs = _struct(L.right)
         # (round 6) the modulation of an odd chirp-z axis moves from G' into the transform that the leaf to its right runs: G' keeps real weights
         kshift, folded, gconst = None, None, 1.0
         if layout == 2 and isinstance(gs, InterpS) and gs.colscale is not None and hasattr(b, 'fold_axis_shifts'):
@@ -351,9 +365,14 @@ class FuseZpadFFT(Transform):
         if Gm is None:
             kshift, folded, gconst = None, None, 1.0
         if Gm is None:
-            Gm = L.right._matrix.astype(np.complex64).tocsr()
-            if layout >= 1:
-                Gm = fused.permute_grid_columns(Gm, grid)
+            if perm is None:
+                Gm = L.right._matrix.astype(np.complex64).tocsr()
+                if layout >= 1:
+                    Gm = fused.permute_grid_columns(Gm, grid)
+            else:
+                # the columns of the recipe's matrix renumbered for the permuted grid (and, layout >= 1, its (x, z, y) order)
+                order = (perm[0], perm[2], perm[1]) if layout >= 1 else tuple(perm)
+                Gm = fused.permute_grid_columns(L.right._matrix.astype(np.complex64).tocsr(), grid0, order)
         zw = fused.support_words(b, grid)
         table = fused.grid_support(Gm, grid, 16, zw) if (layout >= 1 and zw is not None and (layout == 2 or zw == (16, 16))) else None
         # ... and the same matrix as one record per sample, where its modulation is a sign per axis (even grids): the interleaved
@@ -362,12 +381,37 @@ class FuseZpadFFT(Transform):
         wsel = (lambda c0, c1: w[..., c0:c1]) if complex(gconst) == 1.0 else (lambda c0, c1: (w[..., c0:c1] * np.complex64(gconst)).astype(np.complex64))
         A = fused.assemble(b, Gm, grid, box, wsel, C, layout, chunks, table=table, box_lo=lo,
                            name=node._name, zw=zw or (16, 16), sep=sep, kshift=kshift)
+        if perm is not None:
+            A = A * b.AxisPermute(image, perm)
+            A._name = node._name
+            A._image_permutation = tuple(perm)
         A._fused_layout = layout
         return A
 
     @staticmethod
     def layout_of(node):
         return getattr(node, '_fused_layout', 0)
+
+
+def _permuted_interp(b, gs, grid, perm):
+    """the InterpS description of G' on the grid with its axes relabelled by `perm` (trajectory rows, grid and the per-axis phases
+    of a separable column scaling permuted) -- or None where there is no description or its column scaling is not separable
+    (the caller then renumbers the columns of the scipy matrix)"""
+    from indigo_amd.structured import DiagS, InterpS, SepPhase
+    if not isinstance(gs, InterpS) or tuple(gs.N) != tuple(grid):
+        return None
+    N = tuple(int(gs.N[a]) for a in perm)
+    coord = np.asarray(gs.coord)[list(perm)]
+    colscale = None
+    if gs.colscale is not None:
+        sp = gs.colscale.separable()
+        if sp is None or tuple(sp[0].shape) != tuple(grid):
+            return None
+        colscale = DiagS(int(np.prod(N)), [('sep', SepPhase(N, [sp[0].phases[a] for a in perm]))] + ([('const', sp[1])] if sp[1] != 1.0 else []))
+    npts, width, table = gs.npts, gs.width, gs.table
+    dtype = np.float32
+    return InterpS(N, coord, width, table, npts, colscale=colscale,
+                   make_plain=lambda: b._interp_matrix(npts, N, width, table, coord, dtype))
 
 
 def sense_recipe(level=3):
