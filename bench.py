@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmarks of the SENSE hot path on MI355X (BASELINE.json metric and configs).
 
-    python bench.py --gpus N --steps K --warmup W [--config {1,2,3,4,5}] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--config {1,2,3,4,5}] [--dump-outputs DIR] [--full]
 
 Default (`--config 4`, BASELINE.json's metric): one "step" is one evaluation y = A^H A x of the composed
 non-Cartesian SENSE normal operator (the reference's `-O3` tree S' -> FFT -> G' -> G'^H -> IFFT -> S'^H, with S' and
@@ -19,21 +19,27 @@ Other configs (each prints its own JSON line, same contract fields):
     --config 5   SENSE 320^3 x 32 coils on the 512^3 grid (oversampling 1.6), coils sharded over the ranks, 8-coil
                  chunks on a rank (the reference's `batch` hint); `--shard R/W` times rank R's share of a W-rank
                  run on one GPU without communication (per-rank cost of a run that cannot be launched here)
-The default run also reports config 5 for the same N in the `config5` object (`--no-config5` skips it), so the
-driver's N = 1, 2, 4, 8 series carries the 32-coil problem's scaling next to the headline's.
+
+A plain run does only what its headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  `--full` adds
+everything else the benchmark measures or checks: the CPU baselines and parity checks of every config and, on the default
+config, the extra measurements of other configurations -- config 5 for the same N (`config5`: an N = 1, 2, 4, 8 series
+carries the 32-coil problem's scaling next to the headline's) and, at N = 1, configs 2 and 3 (`config2`, `config3`), 8 x the
+spokes (`dense_trajectory`) and kernel half-width 3 (`width3`).  `--no-cpu-baseline`, `--no-config5`, `--no-leaf-configs`,
+`--no-dense` and `--no-extras` take parts of a `--full` run away again.
 
 Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   roofline         : the dominant kernel: algorithmic (compulsory) bytes per launch / average launch duration measured
                      live with HIP events on the backend's stream; `traffic` = HBM bytes per launch from the
                      committed rocprofv3 PMC summary of this same command (profiles/)
+  eval_traffic_*   : bytes the whole evaluation really moves (PMC summary) and the fraction of the 8 TB/s peak that
+                     is; `reference_model_*`: the same evaluation priced with the reference's leaf-by-leaf model
+                     (SURVEY 8d) -- a speed-up measure, NOT a roofline fraction (fusion removed those bytes)
+and with `--full`
   cpu_baseline     : the numpy oracle (restatement of the reference's numpy backend) timed on the host on ONE coil
                      of the same problem (warm-up + min of 5), scaled to evals/s; single-threaded, baseline only
   parity_rel_err   : the benchmarked operator with all coils but one switched off vs that oracle evaluation and vs a
                      double-precision evaluation of the same operator (the complex64 oracle is itself only good to
                      ~2.6e-5 on this DC-heavy input, oracle/precise.py)
-  eval_traffic_*   : bytes the whole evaluation really moves (PMC summary) and the fraction of the 8 TB/s peak that
-                     is; `reference_model_*`: the same evaluation priced with the reference's leaf-by-leaf model
-                     (SURVEY 8d) -- a speed-up measure, NOT a roofline fraction (fusion removed those bytes)
 
 `--dump-outputs DIR` writes, after the timed steps, what the selected config's timed path computed in its last step as
 DIR/<name>.npy (float32, a trailing (re, im) axis; see dump_outputs): the inputs are seeded, so two builds run with the same
@@ -164,7 +170,7 @@ def parse():
                     "reference driver's own scan on the 640 x 277 x 410 grid its sizing rule gives, backend.py:427-430); default 256 / 320 for config 4 / 5")
     ap.add_argument("--spokes-scale", type=float, default=1.0, help="config 4: multiply the number of radial spokes (8: a densely sampled "
                     "scan -- the k-space support table then flags most of the ball)")
-    ap.add_argument("--no-dense", action="store_true", help="default run at N = 1: skip the extra dense-trajectory measurement")
+    ap.add_argument("--no-dense", action="store_true", help="--full on the default config at N = 1: skip the extra dense-trajectory and width-3 measurements")
     ap.add_argument("--coils", type=int, default=0, help="coils (default 8 / 32 for config 4 / 5)")
     ap.add_argument("--width", type=float, default=2.0, help="configs 4 / 5: half-width of the Kaiser-Bessel gridding kernel in grid cells (indigo's "
                     "`width`): 2 = BASELINE's 'width-4' kernel, 27 taps per sample; 3 = the default of the reference's Backend.NUFFT "
@@ -180,14 +186,16 @@ def parse():
     ap.add_argument("--comm", choices=["auto", "rccl", "torch", "direct"], default="auto",
                     help="all-reduce provider for N > 1: the library's own RCCL binding (ig_comm_*), torch.distributed, or direct: the "
                          "library's own reduce-scatter + all-gather over HIP IPC windows (no RCCL; every rank talks to all peers at once)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--parity", action="store_true", help="configs 4 / 5 with --no-cpu-baseline: still check the benchmarked operator against the "
+    ap.add_argument("--full", action="store_true", help="besides the headline, measure and check everything else: CPU baselines, parity "
+                    "against the oracles and, on the default config, the config-5 / config-2 / config-3 / dense-trajectory / width-3 extras")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--parity", action="store_true", help="configs 4 / 5 without the CPU baseline: still check the benchmarked operator against the "
                     "float64 evaluation of a one-coil operator (oracle/precise.py)")
-    ap.add_argument("--no-config5", action="store_true", help="default run: skip the extra config-5 measurement")
-    ap.add_argument("--no-leaf-configs", action="store_true", help="default run at N = 1: skip the extra config-2 / config-3 measurements")
+    ap.add_argument("--no-config5", action="store_true", help="--full on the default config: skip the extra config-5 measurement")
+    ap.add_argument("--no-leaf-configs", action="store_true", help="--full on the default config at N = 1: skip the extra config-2 / config-3 measurements")
     ap.add_argument("--batch", type=int, default=16, help="config 2: number of volumes")
     ap.add_argument("--ncol", type=int, default=64, help="config 3: panel columns")
-    ap.add_argument("--no-extras", action="store_true", help="only the selected config: --no-config5 --no-leaf-configs (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: only the selected config, --no-config5 --no-leaf-configs --no-dense")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the selected config's timed path "
                     "computed in its last step as DIR/<name>.npy (float32 (re, im) pairs; a seeded sample of rows when larger than the budget)")
     args = ap.parse_args()
@@ -195,6 +203,9 @@ def parse():
         ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.no_extras:
         args.no_config5 = args.no_leaf_configs = args.no_dense = True
+    if not args.full:
+        # a plain run: only what the headline needs (configs 1-3 test args.full for their parity checks)
+        args.no_config5 = args.no_leaf_configs = args.no_dense = args.no_cpu_baseline = True
     dims = [int(v) for v in str(args.image).split(",") if v.strip()] if args.image else []
     assert len(dims) in (0, 1, 3), "--image N or --image X,Y,Z"
     args.image_dims = tuple(dims) if len(dims) == 3 else None          # non-cubic image (config 4 only)
@@ -848,13 +859,14 @@ def bench_fft(args, local_rank, B=None):
     pmc, src = load_pmc(2) if n == 256 and batch == 16 else (None, None)
     traffic = sum(pmc[k]["hbm_bytes_per_launch"] * 1.0 for k in pmc if k.startswith("k_fft")) if pmc else None
     inv_elapsed, _ = timed_steps(B, None, lambda: B.ifftn(yv, yv), max(2, args.steps // 2), 1)
-    # parity on the spot: one volume (the fourth when there are that many) against numpy
-    B.fftn(yv, x)
-    pv = min(3, batch - 1)
-    got = yv[:, :, :, pv:pv + 1].to_host()[..., 0]
-    ref = np.fft.fftn(x[:, :, :, pv:pv + 1].to_host()[..., 0])
-    perr = float(np.linalg.norm(got - ref) / np.linalg.norm(ref))
-    cpu = None
+    perr = cpu = None
+    if args.full:
+        # parity on the spot: one volume (the fourth when there are that many) against numpy
+        B.fftn(yv, x)
+        pv = min(3, batch - 1)
+        got = yv[:, :, :, pv:pv + 1].to_host()[..., 0]
+        ref = np.fft.fftn(x[:, :, :, pv:pv + 1].to_host()[..., 0])
+        perr = float(np.linalg.norm(got - ref) / np.linalg.norm(ref))
     if not args.no_cpu_baseline:
         v = x[:, :, :, 0:1].to_host()[..., 0]
         ts = []
@@ -951,15 +963,16 @@ def bench_spmm(args, local_rank, B=None):
         a_traffic = sum(e.get("pmc_bytes_per_launch", e.get("bytes_per_launch") or 0.0) * e["launches_per_step"] for e in ktab_a.values()) or None
         if all("pmc_bytes_per_launch" in e for e in ktab_f.values()):
             traffic = sum(e["pmc_bytes_per_launch"] * e["launches_per_step"] for e in ktab_f.values())
-    # parity: column 5 against scipy, forward and adjoint
-    x5 = X[:, 5:6].to_host()
-    y5 = Y[:, 5:6].to_host()
-    ref = G @ x5
-    perr = float(np.linalg.norm(y5 - ref) / np.linalg.norm(ref))
-    z5 = Z[:, 5:6].to_host()
-    refa = G.conj().T.astype(np.complex128) @ y5.astype(np.complex128)
-    perr_a = float(np.linalg.norm(z5 - refa) / np.linalg.norm(refa))
-    cpu = None
+    perr = perr_a = cpu = None
+    if args.full:
+        # parity: column 5 against scipy, forward and adjoint
+        x5 = X[:, 5:6].to_host()
+        y5 = Y[:, 5:6].to_host()
+        ref = G @ x5
+        perr = float(np.linalg.norm(y5 - ref) / np.linalg.norm(ref))
+        z5 = Z[:, 5:6].to_host()
+        refa = G.conj().T.astype(np.complex128) @ y5.astype(np.complex128)
+        perr_a = float(np.linalg.norm(z5 - refa) / np.linalg.norm(refa))
     if not args.no_cpu_baseline:
         xs = np.asfortranarray(X[:, 0:8].to_host())
         ts = []
@@ -1035,15 +1048,19 @@ def bench_spmm_example(args, local_rank):
     elapsed, prof = timed_steps(B, None, lambda: S.eval(y, x), steps, args.warmup)
     dump_outputs(args.dump_outputs, [("spmm_y", y)])
     ms = elapsed / steps * 1e3
-    O = NumpyBackend()
-    So = O.SpMatrix(A)
-    xo, yo = O.copy_array(xh), O.zero_array((10000, 8), np.dtype('complex64'))
-    ts = []
-    for _ in range(11):
-        t1 = time.perf_counter()
-        So.eval(yo, xo)
-        ts.append(time.perf_counter() - t1)
-    perr = float(np.linalg.norm(y.to_host() - yo.to_host()) / np.linalg.norm(yo.to_host()))
+    cpu = perr = None
+    if args.full:
+        O = NumpyBackend()
+        So = O.SpMatrix(A)
+        xo, yo = O.copy_array(xh), O.zero_array((10000, 8), np.dtype('complex64'))
+        ts = []
+        for _ in range(11):
+            t1 = time.perf_counter()
+            So.eval(yo, xo)
+            ts.append(time.perf_counter() - t1)
+        perr = float(np.linalg.norm(y.to_host() - yo.to_host()) / np.linalg.norm(yo.to_host()))
+        cpu = dict(value=1.0 / min(ts[1:]), unit="products/s", cores=1, kind="port", **host_info(),
+                   sample="numpy oracle SpMatrix.eval, 1 warm-up + min of 10 (%.2f ms)" % (min(ts[1:]) * 1e3))
     nbytes = A.nnz * 12 + 10001 * 4 + 10000 * 8 * 8 * 2
     out = {"metric": "examples/spmm.py: 1e4 x 1e4 CSR (1 % nnz) x 8 RHS SpMM products/sec", "value": steps / elapsed, "unit": "products/s",
            "n_gpus": 1, "steps": steps, "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True, "scaling": "weak",
@@ -1052,9 +1069,7 @@ def bench_spmm_example(args, local_rank):
            "roofline": dict(bound="hbm", kernel="+".join(sorted(prof)), achieved=nbytes / (ms * 1e-3) / 1e9, peak=HBM_PEAK_GBS, unit="GB/s",
                             frac=nbytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, algorithmic_bytes_per_launch=nbytes, traffic=None,
                             note="13 MB: launch-latency bound, fits the L2"),
-           "cpu_baseline": dict(value=1.0 / min(ts[1:]), unit="products/s", cores=1, kind="port", **host_info(),
-                                sample="numpy oracle SpMatrix.eval, 1 warm-up + min of 10 (%.2f ms)" % (min(ts[1:]) * 1e3)),
-           "parity_rel_err": perr, "kernels": kernel_table(prof, steps)}
+           "cpu_baseline": cpu, "parity_rel_err": perr, "kernels": kernel_table(prof, steps)}
     return out
 
 
