@@ -66,6 +66,10 @@ PROTOTYPES = {
     "ig_csum_il":         (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_float, c_float, c_float, c_float, c_void_p]),
     "ig_permute3_c64":    (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                    c_float, c_float, c_float, c_float, c_void_p, c_int64]),
+    "ig_dwt3_c64":        (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int64, c_void_p, c_int64,
+                                   c_float, c_float, c_float, c_float, c_void_p, c_int64]),
+    "ig_csoft_c64":       (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_float,
+                                   c_void_p, c_int64]),
     "ig_ccsrmm_il":       (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64,
                                    c_float, c_float, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_float, c_float, c_void_p, c_int64]),

@@ -34,6 +34,65 @@ log = logging.getLogger(__name__)
 _C64 = np.dtype('complex64')
 
 
+# Daubechies minimum-phase low-pass filters of the wavelet transform (Backend.dwt3, operators.Wavelet); the
+# high-pass filter is g[j] = (-1)^j h[L-1-j].  The same constants are compiled into indigo_amd/csrc/ig_wavelet.hip.
+WAVELETS = {
+    'haar': (2 ** -0.5, 2 ** -0.5),
+    'db2': (0.48296291314453416, 0.8365163037378079, 0.22414386804201339, -0.12940952255126037),
+    'db4': (0.23037781330889645, 0.7148465705529156, 0.630880767929859, -0.027983769416859594,
+            -0.18703481171909306, 0.03084138183556063, 0.032883011666885176, -0.010597401785069018),
+}
+WAVELET_IDS = {'haar': 0, 'db2': 1, 'db4': 2}     # the `wavelet` argument of ig_dwt3_c64
+DWT_MAX_AXIS = 1024
+
+
+def dwt_plan(dims, wavelet, levels):
+    """-> (passes, coarse): the forward passes of the wavelet transform of an F-ordered `dims` volume, in order, as
+    (box before the split, axis split), and the low-pass corner box the last level leaves.  Level 1 splits the whole volume,
+    level l+1 the box level l left; within a level the axes go 0, 1, 2 and an axis splits while its current length is even and
+    at least twice the filter's length.  The transform stops after `levels` levels or at the first level where nothing splits."""
+    taps = len(WAVELETS[wavelet])
+    c = [int(n) for n in dims]
+    assert len(c) == 3, dims
+    passes = []
+    for _ in range(int(levels)):
+        split = False
+        for a in range(3):
+            if c[a] % 2 == 0 and c[a] >= 2 * taps:
+                passes.append((tuple(c), a))
+                c[a] //= 2
+                split = True
+        if not split:
+            break
+    return passes, tuple(c)
+
+
+def dwt_coarse_box(dims, wavelet, levels):
+    """the coarse (approximation) box that `dwt_plan` leaves: the part of the coefficients soft_threshold keeps"""
+    return dwt_plan(dims, wavelet, levels)[1]
+
+
+def _dwt_split(u, h, inverse):
+    """one periodic split along axis 0 of u (complex128, axis 0 of even length d): low to [0, d/2), high to [d/2, d)"""
+    h = np.asarray(h, dtype=np.float64)
+    L, d = h.size, u.shape[0]
+    g = h[::-1] * (-1.0) ** np.arange(L)
+    idx = (2 * np.arange(d // 2)[:, None] + np.arange(L)[None, :]) % d          # (d/2, L)
+    u2 = u.reshape((d, -1))
+    if not inverse:
+        taps = u2[idx]                                                          # (d/2, L, rest)
+        out = np.concatenate([np.einsum('klr,l->kr', taps, h), np.einsum('klr,l->kr', taps, g)])
+    else:
+        # v[2m + r] = sum_i h[2i + r] low[(m - i) mod d/2] + g[2i + r] high[(m - i) mod d/2],  r = 0, 1
+        half = d // 2
+        src = (np.arange(half)[:, None] - np.arange(L // 2)[None, :]) % half    # (d/2, L/2)
+        low, high = u2[:half][src], u2[half:][src]
+        out = np.empty_like(u2)
+        for r in (0, 1):
+            out[r::2] = np.einsum('mir,i->mr', low, h[r::2]) + np.einsum('mir,i->mr', high, g[r::2])
+    return out.reshape(u.shape)
+
+
 class Backend(object):
 
     def __init__(self, device_id=0):
@@ -383,6 +442,10 @@ class Backend(object):
         (see operators.AxisPermute)"""
         return op.AxisPermute(self, dims, perm, **kwargs)
 
+    def Wavelet(self, dims, wavelet='db2', levels=3, **kwargs):
+        """the unitary wavelet transform of an F-ordered `dims` volume (see operators.Wavelet); .H is its inverse"""
+        return op.Wavelet(self, dims, wavelet=wavelet, levels=levels, **kwargs)
+
     def Interp(self, N, coord, width, table, dtype=_C64, **kwargs):
         """gridding / interpolation matrix (npts x prod N) from a k-space trajectory"""
         assert len(N) == 3
@@ -499,6 +562,43 @@ class Backend(object):
         if beta != 0:
             out = (y.to_host().reshape((n, ncols), order='F') * np.complex64(beta) + out).astype(_C64)
         y.copy_from(np.asfortranarray(out.reshape(y.shape, order='F')))
+
+    def dwt3(self, y, x, dims, wavelet, levels, inverse=False, alpha=1, beta=0):
+        """y[:, j] = beta*y[:, j] + alpha * W x[:, j] (inverse: W^H = W^-1) for every column j, W the orthonormal periodic wavelet
+        transform of an F-ordered `dims` volume (`dwt_plan`; filters `WAVELETS`).  y may be x when beta == 0; beta == 0: y is not
+        read.  This host form computes in float64 through to_host / copy_from, so that every backend has it; device backends
+        override it."""
+        dims = tuple(int(n) for n in dims)
+        n = int(np.prod(dims))
+        assert x.size % n == 0 and x.size == y.size, (x.shape, y.shape, dims)
+        ncols = x.size // n
+        passes, _ = dwt_plan(dims, wavelet, levels)
+        v = x.to_host().reshape(dims + (ncols,), order='F').astype(np.complex128)
+        for box, a in (reversed(passes) if inverse else passes):
+            sl = tuple(slice(0, c) for c in box)
+            u = np.moveaxis(v[sl], a, 0)
+            v[sl] = np.moveaxis(_dwt_split(u, WAVELETS[wavelet], inverse), 0, a)
+        out = v.reshape((n, ncols), order='F') * complex(alpha)
+        if beta != 0:
+            out = out + complex(beta) * y.to_host().reshape((n, ncols), order='F')
+        y.copy_from(np.asfortranarray(out.astype(_C64).reshape(y.shape, order='F')))
+
+    def soft_threshold(self, x, tau, dims, keep):
+        """x <- x * max(0, 1 - tau / |x|) in place, column by column, for every element of the F-ordered `dims` volume outside the
+        box [0, keep[0]) x [0, keep[1]) x [0, keep[2]) (the wavelet transform's coarse band, `dwt_coarse_box`), which is left
+        untouched.  |x| <= tau gives exactly 0.  Host form through to_host / copy_from; device backends override it."""
+        dims = tuple(int(n) for n in dims)
+        n = int(np.prod(dims))
+        assert x.size % n == 0 and tau >= 0, (x.shape, dims, tau)
+        v = x.to_host().reshape(dims + (-1,), order='F')
+        out = v.astype(np.complex128)
+        r2 = out.real ** 2 + out.imag ** 2
+        with np.errstate(divide='ignore', invalid='ignore'):
+            f = np.where(r2 <= float(tau) ** 2, 0.0, 1.0 - float(tau) / np.sqrt(r2))
+        inside = np.zeros(dims, dtype=bool)
+        inside[tuple(slice(0, int(c)) for c in keep)] = True
+        out = np.where(inside[..., None], v, (out * f).astype(_C64))
+        x.copy_from(np.asfortranarray(out.astype(_C64).reshape(x.shape, order='F')))
 
     def supports_padded_fft(self, grid, ncoils=None):
         """whether `fft_padded` / `ifft_cropped[_sum]` exist for this oversampled grid (and, if given, this many coils)"""
@@ -680,6 +780,39 @@ class Backend(object):
         if not in_place:
             x.copy_to(x_h)
         return trail
+
+    def fista(self, gradf, proxg, alpha, x_h, maxiter=100, callback=None):
+        """FISTA (Beck and Teboulle 2009) for min f + g with a fixed step `alpha`:
+
+            x_{k+1} = prox_{alpha g}(z_k - alpha grad f(z_k)),   t_{k+1} = (1 + sqrt(1 + 4 t_k^2)) / 2,   t_0 = 1,
+            z_{k+1} = x_{k+1} + m_k (x_{k+1} - x_k),             m_k = (t_k - 1) / t_{k+1},                z_0 = x_0.
+
+        gradf(g, z) writes grad f(z) into g; proxg(v, alpha) replaces v by prox_{alpha g}(v).  x_h is the start and receives the
+        result (a host array, or a device array of this backend, updated in place).  callback(k, x), when given, runs after
+        iteration k (from 0) with the iterate x_{k+1}.  Three vectors; besides gradf and proxg an iteration is two axpby passes
+        (the gradient step into g's buffer, the extrapolation into x_k's buffer, then the three buffers change roles), so on a
+        device backend it enqueues work and never waits for the device.  Unlike `apgd`, whose momentum is the reference's
+        constant 0, this one advances t_k."""
+        in_place = isinstance(x_h, self.dndarray)
+        x = x_h if in_place else self.copy_array(x_h, name='x')
+        x_out = x
+        z, g = x.copy(name='z'), x.copy(name='g')
+        t = 1.0
+        for k in range(int(maxiter)):
+            gradf(g, z)
+            self.axpby(-alpha, g, 1, z)                # g <- z - alpha grad f(z)
+            proxg(g, alpha)                            # g <- x_{k+1}
+            t_next = 0.5 * (1.0 + np.sqrt(1.0 + 4.0 * t * t))
+            m = (t - 1.0) / t_next
+            self.axpby(-m, x, 1 + m, g)                # x_k's buffer <- z_{k+1}
+            x, z, g = g, x, z
+            t = t_next
+            if callback is not None:
+                callback(k, x)
+        if x is not x_out:
+            x_out.copy(x)
+        if not in_place:
+            x_out.copy_to(x_h)
 
     def apgd(self, gradf, proxg, alpha, x_h, maxiter=100, team=None):
         """Proximal gradient iteration for min f + g:  x <- prox_g(x - alpha grad f(y)),  y <- x + m (x - x_before).

@@ -17,7 +17,7 @@ import os
 import numpy as np
 
 from indigo_amd import _lib
-from indigo_amd.backends.backend import Backend
+from indigo_amd.backends.backend import WAVELET_IDS, Backend
 
 log = logging.getLogger(__name__)
 _C64 = np.dtype('complex64')
@@ -860,6 +860,29 @@ class HipBackend(Backend):
         br, bi = _cplx(beta)
         self._check(self._L.ig_permute3_c64(self._ctx, n0, n1, n2, p, ncols, ctypes.c_void_p(x._arr), x._leading_dim,
                                             ar, ai, br, bi, ctypes.c_void_p(y._arr), y._leading_dim), "ig_permute3_c64")
+
+    def dwt3(self, y, x, dims, wavelet, levels, inverse=False, alpha=1, beta=0):
+        """Backend.dwt3 on the device (ig_dwt3_c64): panels of any column count with their leading dimensions; y may be x"""
+        assert x.dtype == _C64 and y.dtype == _C64, "only complex64 is supported"
+        n0, n1, n2 = (int(n) for n in dims)
+        n = n0 * n1 * n2
+        assert x.shape[0] == n and y.shape[0] == n and x.size == y.size, (x.shape, y.shape, dims)
+        ncols = x.shape[1] if x.ndim == 2 else 1
+        ar, ai = _cplx(alpha)
+        br, bi = _cplx(beta)
+        self._check(self._L.ig_dwt3_c64(self._ctx, n0, n1, n2, WAVELET_IDS[wavelet], int(levels), int(bool(inverse)), ncols,
+                                        ctypes.c_void_p(x._arr), x._leading_dim, ar, ai, br, bi,
+                                        ctypes.c_void_p(y._arr), y._leading_dim), "ig_dwt3_c64")
+
+    def soft_threshold(self, x, tau, dims, keep):
+        """Backend.soft_threshold on the device (ig_csoft_c64), in place"""
+        assert x.dtype == _C64, "only complex64 is supported"
+        n0, n1, n2 = (int(n) for n in dims)
+        assert x.shape[0] == n0 * n1 * n2, (x.shape, dims)
+        ncols = x.shape[1] if x.ndim == 2 else 1
+        c0, c1, c2 = (int(c) for c in keep)
+        self._check(self._L.ig_csoft_c64(self._ctx, n0, n1, n2, c0, c1, c2, ncols, ctypes.c_float(float(tau)),
+                                         ctypes.c_void_p(x._arr), x._leading_dim), "ig_csoft_c64")
 
     def fftn(self, y, x):
         self._fft(y, x, -1)

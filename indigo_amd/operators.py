@@ -511,6 +511,39 @@ class AxisPermute(MatrixFreeOperator):
         self._backend.permute3(y, x, dims, perm, alpha=alpha, beta=beta)
 
 
+class Wavelet(MatrixFreeOperator):
+    """The orthonormal periodic multi-level wavelet transform of an F-ordered complex64 volume of shape `dims` (2-D: dims[2] == 1),
+    shape (N, N): Daubechies filters 'haar', 'db2' or 'db4' (backend.WAVELETS), at most `levels` levels (backend.dwt_plan),
+    coefficients in place of the samples, the coarse approximation band in the corner box `coarse`.  Unitary: .H is the inverse.
+    Every axis is at most 1024 long (the HIP kernel stages whole lines in LDS).  The sparsifying transform of pics --l1."""
+
+    def __init__(self, backend, dims, wavelet='db2', levels=3, **kwargs):
+        from indigo_amd.backends.backend import DWT_MAX_AXIS, WAVELETS, dwt_plan
+        self._dims = tuple(int(n) for n in dims)
+        if len(self._dims) != 3 or min(self._dims) < 1:
+            raise ValueError("Wavelet: dims must be three positive lengths, got %s" % (dims,))
+        if max(self._dims) > DWT_MAX_AXIS:
+            raise ValueError("Wavelet: axes are at most %d long, got %s" % (DWT_MAX_AXIS, self._dims))
+        if wavelet not in WAVELETS:
+            raise ValueError("Wavelet: unknown wavelet %r (one of %s)" % (wavelet, ", ".join(sorted(WAVELETS))))
+        self._wavelet, self._levels = wavelet, int(levels)
+        passes, self.coarse = dwt_plan(self._dims, wavelet, self._levels)
+        self._pass_elems = sum(int(np.prod(box)) for box, _ in passes)
+        n = int(np.prod(self._dims))
+        kwargs.setdefault('name', 'wavelet(%s, %d)' % (wavelet, self._levels))
+        super().__init__(backend, shape=(n, n), **kwargs)
+
+    def _eval(self, y, x, alpha=1, beta=0, forward=True, left=True):
+        trace = getattr(self._backend, 'trace', None)
+        if trace is not None:
+            # every split pass reads and writes its box once (16 B per element); beta != 0 runs the transform twice
+            # (y = beta y + alpha W x = W (beta W^H y + alpha x)) around a combining pass
+            ncols = x.shape[1]
+            nbytes = 16 * self._pass_elems * ncols * (1 if beta == 0 else 2) + (0 if beta == 0 else 24 * self.shape[0] * ncols)
+            trace.add('wavelet', nbytes=nbytes, nflops=0, shape=x.shape, forward=forward, name=self._name)
+        self._backend.dwt3(y, x, self._dims, self._wavelet, self._levels, inverse=not forward, alpha=alpha, beta=beta)
+
+
 class Eye(MatrixFreeOperator):
     def __init__(self, backend, n, **kwargs):
         super().__init__(backend, shape=(n, n), **kwargs)

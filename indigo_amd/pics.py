@@ -2,6 +2,7 @@
 """Parallel-imaging reconstruction driver: non-Cartesian SENSE by conjugate gradients.
 
     python -m indigo_amd.pics [-i ITER] [--lamda L] [-O LEVEL] [--crop "COIL:2,TIME:1"] [--no-fuse] scan.h5 | scan.npz
+    python -m indigo_amd.pics --l1 LAMBDA [--wavelet db2] [--levels 3] [--step S | --power-iters 15] ... scan.npz
 
 The counterpart of the reference's driver script (examples/pics.py:20-95 arguments, data layout and tree
 construction, :179-233 recipe, normal equations, CG, output): reads `data` (k-space), `maps` (coil sensitivities)
@@ -12,6 +13,13 @@ and `traj` (trajectory, in units of 1/FOV pixels) with the reference's BART-styl
 builds  A = KronI(C, NUFFT) * VStack(Diag(maps_c)),  rewrites it with `sense_recipe(level)` (= pics.py -O<level>),
 and -- where the backend has zero-pad-aware transforms for the grid -- `FuseZpadFFT`, solves
 (A^H A + lamda I) x = A^H y with `Backend.cg`, and writes the image back as `rec`.
+
+With `--l1 LAMBDA > 0` (compressed sensing, no counterpart in the reference's driver; `bart pics -R W`) it solves instead
+
+    min_x  1/2 ||A x - y||^2 + lamda/2 ||x||^2 + LAMBDA ||W x||_1        (W: operators.Wavelet, coarse band not penalised)
+
+by `Backend.fista` on the same A and the same normalised A^H y, with the fixed step 0.9 / (largest eigenvalue of
+A^H A + lamda I, from `--power-iters` power iterations) unless `--step` gives one.
 
 Containers: HDF5 (`.h5`, the reference's format; needs h5py, which this image does not ship) or NumPy `.npz` with
 the same three arrays in the same orientation; the result goes back into the HDF5 file as dataset `rec`, or next to
@@ -27,6 +35,8 @@ import sys
 
 import numpy as np
 
+from indigo_amd.util import rand64c
+
 log = logging.getLogger("pics")
 
 
@@ -35,7 +45,7 @@ class dim:
 
 
 def parse(argv):
-    ap = argparse.ArgumentParser(prog="indigo_amd.pics", description="Parallel Imaging and Compressed Sensing (non-Cartesian SENSE, CG).")
+    ap = argparse.ArgumentParser(prog="indigo_amd.pics", description="Parallel Imaging and Compressed Sensing (non-Cartesian SENSE: CG, or L1-wavelet FISTA).")
     ap.add_argument('-i', type=int, default=20, help='number of CG iterations')
     ap.add_argument('--backend', type=str, default='hip', choices=['hip'])
     ap.add_argument('--device', type=int, default=0)
@@ -46,6 +56,11 @@ def parse(argv):
     ap.add_argument('--osf', type=float, default=640 / 480, help='gridding oversampling factor (pics.py: 640/480)')
     ap.add_argument('--width', type=int, default=3, help='Kaiser-Bessel kernel half-width (Backend.NUFFT default)')
     ap.add_argument('--no-fuse', action='store_true', help='keep the -O tree as it is (no FuseZpadFFT)')
+    ap.add_argument('--l1', type=float, default=0, help='L1-wavelet weight; > 0 solves by FISTA instead of CG (0: CG)')
+    ap.add_argument('--wavelet', default='db2', choices=['haar', 'db2', 'db4'], help='wavelet of --l1')
+    ap.add_argument('--levels', type=int, default=3, help='wavelet levels of --l1')
+    ap.add_argument('--power-iters', type=int, default=15, help='power iterations that estimate the FISTA step')
+    ap.add_argument('--step', type=float, default=None, help='FISTA step (default 0.9 / the power-iteration estimate)')
     ap.add_argument('data', nargs='?', default="scan.h5", help='k-space data: HDF5 (data/maps/traj) or .npz')
     return ap.parse_args(argv)
 
@@ -82,8 +97,77 @@ def crop_limits(spec):
     return crops
 
 
-def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, width=3, fuse=True):
-    """ksp: (1, readout, views, C, 1, ...), mps: (X, Y, Z, C, 1), traj: (3, readout, views) in pixels -> image (X, Y, Z, 1, ...)"""
+def power_iteration(B, AHA, iters, seed=0):
+    """largest eigenvalue of the Hermitian positive semi-definite AHA: `iters` power iterations from a seeded random start,
+    the estimate ||AHA v|| for the last unit vector v"""
+    n = AHA.shape[1]
+    v = B.copy_array(rand64c(n, 1, seed=seed), name='power.v')
+    w = B.zero_array((n, 1), np.dtype('complex64'), name='power.w')
+    B.scale(v, 1.0 / np.sqrt(B.norm2(v)))
+    lam = 0.0
+    for _ in range(int(iters)):
+        AHA.eval(w, v)
+        lam = float(np.sqrt(B.norm2(w)))
+        if lam == 0:
+            break
+        B.axpby(0, v, 1.0 / lam, w)
+    return lam
+
+
+def fista_solve(B, AHA, AHy, dims, iters, l1, wavelet='db2', levels=3, power_iters=15, step=None, ynorm2=0.0):
+    """min_x 1/2 x^H AHA x - Re(x^H AHy) + ynorm2 / 2 + l1 ||W x||_1 (W's coarse band excluded) by Backend.fista from x = 0;
+    with AHA = A^H A + lamda I and AHy = A^H y that is 1/2 ||A x - y||^2 + lamda/2 ||x||^2 + l1 ||W x||_1 for ynorm2 = ||y||^2.
+    Returns the image as a host (N, 1) array and the objectives logged: [(iteration, value)], every 10 iterations and the last."""
+    c64 = np.dtype('complex64')
+    W = B.Wavelet(dims, wavelet=wavelet, levels=levels)
+    if step is None:
+        lam = power_iteration(B, AHA, power_iters)
+        step = 0.9 / lam
+        log.info("fista: largest eigenvalue of A^H A + lamda I %.6e (%d power iterations), step %.6e", lam, power_iters, step)
+    else:
+        log.info("fista: step %.6e (given)", step)
+    log.info("fista: %s wavelet, %d levels, coarse box %s of %s, l1 %g", wavelet, levels, W.coarse, tuple(dims), l1)
+    n = AHA.shape[1]
+    b = B.copy_array(AHy, name='AHy')
+
+    def gradf(g, z):
+        AHA.eval(g, z)
+        B.axpby(1, g, -1, b)
+
+    def proxg(v, alpha):
+        W.eval(v, v)
+        B.soft_threshold(v, alpha * l1, dims, W.coarse)
+        W.H.eval(v, v)
+
+    objectives = []
+    work = {}
+
+    def objective(k, x):
+        if not (k % 10 == 9 or k == iters - 1) or not log.isEnabledFor(logging.INFO):
+            return
+        if not work:
+            work['q'] = B.zero_array((n, 1), c64, name='objective.q')
+            work['w'] = B.zero_array((n, 1), c64, name='objective.w')
+        q, w = work['q'], work['w']
+        AHA.eval(q, x)
+        W.eval(w, x)
+        coef = w.to_host().reshape(tuple(dims), order='F')
+        inside = np.zeros(tuple(dims), dtype=bool)
+        inside[tuple(slice(0, c) for c in W.coarse)] = True
+        l1_term = float(np.abs(coef[~inside].astype(np.complex128)).sum())
+        val = 0.5 * B.dot(x, q) - B.dot(x, b) + 0.5 * ynorm2 + l1 * l1_term
+        objectives.append((k + 1, val))
+        log.info("fista iter %d, objective %.9e", k + 1, val)
+
+    x = np.zeros((n, 1), dtype=c64, order='F')
+    B.fista(gradf, proxg, step, x, maxiter=iters, callback=objective)
+    return x, objectives
+
+
+def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, width=3, fuse=True,
+                l1=0.0, wavelet='db2', levels=3, power_iters=15, step=None):
+    """ksp: (1, readout, views, C, 1, ...), mps: (X, Y, Z, C, 1), traj: (3, readout, views) in pixels -> image (X, Y, Z, 1, ...)
+    l1 > 0: L1-wavelet regularised by FISTA (`fista_solve`), else CG on the normal equations"""
     from indigo_amd.transforms import FuseZpadFFT, Optimize, sense_recipe
     from indigo_amd.transforms import reserve_for
     ksp = np.asarray(ksp, dtype=np.complex64)
@@ -115,7 +199,13 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
     log.info('using %d MB of device memory', (AHA.memusage() + 4 * AHA.shape[1] * ksp.dtype.itemsize) / 1e6)
     y = np.asfortranarray(ksp.reshape((-1, 1), order='F'))
     AHy = A.H * y
-    AHy /= abs(AHy).max()
+    scale = abs(AHy).max()
+    AHy /= scale
+    if l1 > 0:
+        ynorm2 = float(np.vdot(y, y).real) / float(scale) ** 2          # the data term of the same normalised problem
+        x, _ = fista_solve(B, AHA, AHy, mps.shape[:3], iters, l1, wavelet=wavelet, levels=levels, power_iters=power_iters,
+                           step=step, ynorm2=ynorm2)
+        return x.reshape(img_dims, order='F')
     x = np.zeros((AHA.shape[1], 1), dtype=ksp.dtype, order='F')
     hist = B.cg(AHA, AHy, x, maxiter=iters)
     log.info("residuals: %s", " ".join("%.3e" % h for h in (hist or [])))
@@ -135,7 +225,8 @@ def main(argv=None, backend=None):
     mps = maps[tuple(slice(0, min(n, c)) for n, c in zip(maps.shape, crops[-maps.ndim:]))].T
     trj = traj[tuple(slice(0, min(n, c)) for n, c in zip(traj.shape, crops[-traj.ndim:]))].T
     img = reconstruct(backend, ksp, mps, trj, iters=args.i, lamda=args.lamda, level=args.recipe, osf=args.osf,
-                      width=args.width, fuse=not args.no_fuse)
+                      width=args.width, fuse=not args.no_fuse, l1=args.l1, wavelet=args.wavelet, levels=args.levels,
+                      power_iters=args.power_iters, step=args.step)
     write(img.T)
     log.info("reconstruction complete")
     return img
