@@ -201,6 +201,12 @@ def last_error(ctx=None):
     return msg.decode("utf-8", "replace") if msg else ""
 
 
+def cplx(v):
+    """a complex scalar as the (re, im) pair of c_float arguments the library's products take"""
+    v = complex(v)
+    return ctypes.c_float(v.real), ctypes.c_float(v.imag)
+
+
 def check(rc, ctx=None, what=""):
     """Status int -> RuntimeError carrying ig_last_error (reference: cuda.py:42-49)."""
     if rc != IG_OK:

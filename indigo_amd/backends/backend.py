@@ -653,6 +653,7 @@ class Backend(object):
             nzrow, nzcol, self._exwrite = backend.inspect(A)
             self._row_frac = nzrow / A.shape[0] if A.shape[0] else 1.0
             self._col_frac = nzcol / A.shape[1] if A.shape[1] else 1.0
+            self._grid_il = False       # set_grid_interleaved
 
         @staticmethod
         def _check_panels(y, x, vals):
@@ -663,14 +664,14 @@ class Backend(object):
         def forward(self, y, x, alpha=1, beta=0):
             """y = alpha * A * x + beta * y"""
             self._check_panels(y, x, self.values)
-            il = {'x_il': True} if getattr(self, '_grid_il', False) else {}
+            il = {'x_il': True} if self._grid_il else {}
             self._backend.ccsrmm(y, self.shape, self.colInds, self.rowPtrs, self.values,
                                  x, alpha=alpha, beta=beta, adjoint=False, exwrite=True, **il)
 
         def adjoint(self, y, x, alpha=1, beta=0):
             """y = alpha * A^H * x + beta * y"""
             self._check_panels(y, x, self.values)
-            il = {'y_il': True} if getattr(self, '_grid_il', False) else {}
+            il = {'y_il': True} if self._grid_il else {}
             self._backend.ccsrmm(y, self.shape, self.colInds, self.rowPtrs, self.values,
                                  x, alpha=alpha, beta=beta, adjoint=True, exwrite=self._exwrite, **il)
 

@@ -17,66 +17,12 @@ import os
 import numpy as np
 
 from indigo_amd import _lib
+from indigo_amd._lib import cplx as _cplx
 from indigo_amd.backends.backend import WAVELET_IDS, Backend
+from indigo_amd.grid_formats import brick_tasks, weights_are_real       # noqa: F401  (their home; imported from here by tools and tests)
 
 log = logging.getLogger(__name__)
 _C64 = np.dtype('complex64')
-
-
-def weights_are_real(data):
-    """True when the imaginary parts of a complex64 array are nothing but rounding residue: at most 2^-34 of the largest magnitude
-    (the residue of exp(2 pi i phase) for a phase of some hundred half turns is ~1e-13 relative; 2^-34 = 5.8e-11 is still a thousand
-    times below the float32 rounding of the products it would enter)"""
-    if data.size == 0:
-        return False
-    im = float(np.abs(data.imag).max())
-    return im == 0.0 or im <= float(np.abs(data.real).max()) * 2.0 ** -34
-
-
-def brick_tasks(counts, ptr, chunk, run, max_bricks=64, longest_first=True):
-    """Task list and brick table of ig_ccsrmm_t_bricks (include/indigo_hip.h) from the entries per brick `counts` and their
-    prefix sums `ptr`: table = (brick, end of its entries) per non-empty brick; a brick with more than `chunk` entries is
-    cut into shared tasks of at most `chunk`; the others are grouped into runs of consecutive table rows -- a new run
-    starts when the entry offset crosses a multiple of `run`, after a heavy brick, and after `max_bricks` bricks.  Returns
-    tasks (n, 4) int32 [lo, hi, first table row, rows | shared << 16] sorted longest first (or, longest_first=False, in
-    brick order), table (nb, 2) int32, and the ids of the shared bricks."""
-    bricks = np.flatnonzero(counts)
-    if bricks.size == 0:
-        return np.zeros((0, 4), np.int32), np.zeros((0, 2), np.int32), np.zeros(0, np.int32)
-    cnt = counts[bricks].astype(np.int64)
-    lo_b, hi_b = ptr[bricks], ptr[bricks + 1]
-    table = np.stack([bricks, hi_b], axis=1).astype(np.int32)
-    heavy = cnt > chunk
-    # runs of light bricks
-    light = np.flatnonzero(~heavy)
-    key = np.cumsum(heavy)[light] * (int(ptr[-1]) // max(run, 1) + 2) + lo_b[light] // max(run, 1)
-    new_run = np.ones(light.size, dtype=bool)
-    new_run[1:] = key[1:] != key[:-1]
-    run_id = np.cumsum(new_run) - 1
-    first_of_run = np.flatnonzero(new_run)
-    rank = np.arange(light.size) - first_of_run[run_id]
-    new_run |= (rank % max_bricks) == 0
-    starts = np.flatnonzero(new_run)
-    ends = np.append(starts[1:], light.size) - 1
-    t_run = np.stack([lo_b[light[starts]], hi_b[light[ends]], light[starts], ends - starts + 1], axis=1) if light.size else np.zeros((0, 4), np.int64)
-    # pieces of heavy bricks
-    hv = np.flatnonzero(heavy)
-    npiece = (cnt[hv] + chunk - 1) // chunk
-    rep = np.repeat(np.arange(hv.size), npiece)
-    firstp = np.concatenate(([0], np.cumsum(npiece)[:-1])) if hv.size else np.zeros(0, np.int64)
-    part = np.arange(rep.size) - firstp[rep]
-    plo = lo_b[hv][rep] + part * chunk
-    phi = np.minimum(plo + chunk, hi_b[hv][rep])
-    t_hv = np.stack([plo, phi, hv[rep], np.full(rep.size, 1 | (1 << 16))], axis=1) if rep.size else np.zeros((0, 4), np.int64)
-    tasks = np.concatenate([t_hv, t_run]).astype(np.int32)
-    order = np.argsort(-(tasks[:, 1] - tasks[:, 0]), kind='stable') if longest_first else np.argsort(tasks[:, 0], kind='stable')
-    tasks = np.ascontiguousarray(tasks[order])
-    return tasks, np.ascontiguousarray(table), bricks[hv].astype(np.int32)
-
-
-def _cplx(v):
-    v = complex(v)
-    return ctypes.c_float(v.real), ctypes.c_float(v.imag)
 
 
 class HipBackend(Backend):
@@ -1030,615 +976,8 @@ class HipBackend(Backend):
         _lib.check(rc, None, "ig_csr_transpose")
         return pt, it, dt
 
-    class csr_matrix(Backend.csr_matrix):
-        """Device CSR with an optional cached CSR of the transpose for gather-form adjoints."""
 
-        def __init__(self, backend, A, name='mat'):
-            super().__init__(backend, A, name)
-            self._host_csr = A if A.dtype == _C64 else A.astype(_C64)   # kept until the transpose is built
-            self._t = None
+# the device CSR matrix and the formats of a gridding matrix: backends/hip_csr.py (it needs nothing of this module)
+from indigo_amd.backends.hip_csr import csr_matrix as _csr_matrix       # noqa: E402
 
-        def _transposed(self):
-            if self._t is None:
-                b = self._backend
-                pt, it, dt = b.csr_transpose(self._host_csr)
-                self._t = (b.copy_array(pt, name=self._name + ".T.rowPtrs"),
-                           b.copy_array(it, name=self._name + ".T.colInds"),
-                           b.copy_array(dt, name=self._name + ".T.data"))
-                self._host_csr = None
-            return self._t
-
-        def set_grid_support(self, table, n0, nm, zw=16):
-            """zw: words per entry of the table's bitmaps (the input-side form, ig_grid_support); 16 for 256- / 512-point nm"""
-            self._support = (self._backend.copy_array(np.ascontiguousarray(table, dtype=np.int16).reshape(-1),
-                                                      name=self._name + ".support"), int(n0), int(nm))
-            self._support_zw = int(zw)
-            self._support_host = table
-
-        def set_grid_support_fine(self, table, tile, ncols=None):
-            """a support table with `tile` (8 or 4) kx points per entry: what the brick scatter writes by (the gather routes keep
-            the 16-point table of set_grid_support; a reader with the finer table reads a subset of what they write).
-            ncols: the panel width whose adjoint writes by this table (a matrix shared by coil chunks of several widths carries
-            one table per width); None = every width without a table of its own."""
-            built = getattr(self, '_bricks_by', {})
-            assert not (any(v is not None for v in built.values()) if ncols is None else built.get(int(ncols)) is not None), \
-                "set_grid_support_fine must come before set_grid_bricks: the runs of bricks are sized for the table's segments"
-            assert int(tile) in (4, 8, 16)
-            self._support_fine = (self._backend.copy_array(np.ascontiguousarray(table, dtype=np.int16).reshape(-1),
-                                                           name=self._name + ".supportFine"), int(tile))
-            self.__dict__.setdefault('_support_fine_by', {})[None if ncols is None else int(ncols)] = self._support_fine
-            self.__dict__.setdefault('_support_fine_host_by', {})[None if ncols is None else int(ncols)] = (table, int(tile))
-
-        def _format(self, which, ncols, exact=False):
-            """the binned format ('_bricks' / '_slots') or fine table ('_support_fine') registered for panels of `ncols` columns"""
-            by = getattr(self, which + '_by', None)
-            if by is None:
-                return None
-            key = None if ncols is None else int(ncols)
-            if key in by or exact:
-                return by.get(key)
-            return by.get(None)
-
-        def set_grid_bricks(self, n0, nm, ns, ncols=8, bm=2, bs=2, chunk=4096, run=4096):
-            """Sort the nonzeros by the 16 x bm x bs brick of the n0 x nm x ns grid their column falls into (native host
-            routine), padded so that a wave instruction (64/ncols entries x ncols panel columns) holds entries of one row
-            only, and keep entries + brick table + task list on the device: the adjoint of an `ncols`-column interleaved
-            panel then scatters brick by brick through LDS (ig_ccsrmm_t_bricks) and needs neither the transposed matrix nor
-            its 4-bytes-per-grid-point row pointers.  A task (one wave) is a run of consecutive non-empty bricks of about
-            `run` entries, or a piece of at most `chunk` entries of a heavy brick (more than `chunk` entries: shared)."""
-            b = self._backend
-            A = self._host_csr
-            assert A is not None and A.shape[1] == n0 * nm * ns and ncols in (4, 8) and bm * bs <= 32
-            unit = 64 // ncols
-            chunk = max(unit, chunk // unit * unit)
-            indptr = np.ascontiguousarray(A.indptr, dtype=np.int32)
-            indices = np.ascontiguousarray(A.indices, dtype=np.int32)
-            data = np.ascontiguousarray(A.data, dtype=_C64)
-            nb = (n0 // 16) * (nm // bm) * (ns // bs)
-            counts = np.zeros(nb, dtype=np.int32)
-            if b._L.ig_grid_bricks_count(A.shape[0], indptr.ctypes.data, indices.ctypes.data, n0, nm, ns, bm, bs, unit,
-                                         counts.ctypes.data) != 0:
-                # e.g. a row that touches more than 64 bricks (very wide gridding kernels): the gather over the transpose serves it
-                log.info("%s: no brick-binned format (%s); the adjoint keeps the gather route", self._name,
-                         _lib.last_error(None) if hasattr(_lib, 'last_error') else "ig_grid_bricks_count failed")
-                self._bricks = None
-                self.__dict__.setdefault('_bricks_by', {})[int(ncols)] = None
-                return
-            ptr = np.zeros(nb + 1, dtype=np.int64)
-            np.cumsum(counts, out=ptr[1:])
-            assert ptr[-1] < 2**31, "brick entries are addressed with 32 bits"
-            entries = np.empty((max(int(ptr[-1]), 1), 3), dtype=np.uint32)
-            round_rows = np.empty(max(int(ptr[-1]) // unit, 1), dtype=np.uint32)
-            _lib.check(b._L.ig_grid_bricks_fill(A.shape[0], indptr.ctypes.data, indices.ctypes.data, data.ctypes.data, n0, nm, ns,
-                                                bm, bs, unit, ptr.ctypes.data, entries.ctypes.data, round_rows.ctypes.data),
-                       None, "ig_grid_bricks_fill")
-            fine = self._format('_support_fine', ncols)
-            nseg = (16 // (fine[1] if fine is not None else 16)) * bm * bs          # segments per brick (the kernel looks up 512 per run)
-            tasks, table, shared = brick_tasks(counts, ptr, chunk, run, max_bricks=min(64, 512 // nseg))
-            # Real weights (a gridding matrix times the +-1 modulation of a centred transform on an even grid, whose imaginary parts
-            # are the 1e-16 rounding residue of exp(i pi k)): 8-byte entries {cell, re}
-            words = 3
-            if self._real_weights(data):
-                entries = np.ascontiguousarray(entries[:, :2])
-                words = 2
-            self._bricks = dict(n0=int(n0), nm=int(nm), bm=int(bm), bs=int(bs), ncols=int(ncols), ntasks=int(tasks.shape[0]), words=words,
-                                nshared=int(shared.size), nentries=int(ptr[-1]),
-                                tasks=b.copy_array(tasks.reshape(-1) if tasks.size else np.zeros(4, np.int32), name=self._name + ".brickTasks"),
-                                table=b.copy_array(table.reshape(-1) if table.size else np.zeros(2, np.int32), name=self._name + ".brickTable"),
-                                entries=b.copy_array(entries.reshape(-1), name=self._name + ".brickEntries"),
-                                rounds=b.copy_array(round_rows, name=self._name + ".brickRoundRows"),
-                                shared=b.copy_array(shared if shared.size else np.zeros(1, np.int32), name=self._name + ".sharedBricks"))
-            self.__dict__.setdefault('_bricks_by', {})[int(ncols)] = self._bricks
-
-        def set_grid_slots(self, n0, nm, ns, ncols=1, bm=2, bs=2, chunk=256, run=128):
-            """The slot format of ig_ccsrmm_t_slots for an `ncols`-column panel (1, 2 or 4): the nonzeros binned by 16 x bm x bs
-            bricks of the n0 x nm x ns grid WITHOUT padding (ig_grid_bricks_count / _fill, unit 1), reordered inside every brick so
-            that a slot of at most 64 entries never holds a cell twice (ig_grid_slots_build), tasks = runs of about `run` slots
-            of consecutive bricks, heavy bricks (more than `chunk` slots) cut into shared pieces."""
-            b = self._backend
-            A = self._host_csr
-            assert A is not None and A.shape[1] == n0 * nm * ns and ncols in (1, 2, 4)
-            indptr = np.ascontiguousarray(A.indptr, dtype=np.int32)
-            indices = np.ascontiguousarray(A.indices, dtype=np.int32)
-            data = np.ascontiguousarray(A.data, dtype=_C64)
-            nb = (n0 // 16) * (nm // bm) * (ns // bs)
-            counts = np.zeros(nb, dtype=np.int32)
-            if b._L.ig_grid_bricks_count(A.shape[0], indptr.ctypes.data, indices.ctypes.data, n0, nm, ns, bm, bs, 1, counts.ctypes.data) != 0 \
-                    or int(counts.sum(dtype=np.int64)) * 16 >= 2 ** 31:
-                log.info("%s: no slot format; the adjoint keeps the gather route", self._name)
-                self._slots = None
-                self.__dict__.setdefault('_slots_by', {})[int(ncols)] = None
-                return
-            ptr = np.zeros(nb + 1, dtype=np.int64)
-            np.cumsum(counts, out=ptr[1:])
-            nent = int(ptr[-1])
-            e12 = np.empty((max(nent, 1), 3), dtype=np.uint32)
-            rows = np.empty(max(nent, 1), dtype=np.uint32)
-            _lib.check(b._L.ig_grid_bricks_fill(A.shape[0], indptr.ctypes.data, indices.ctypes.data, data.ctypes.data, n0, nm, ns, bm, bs, 1,
-                                                ptr.ctypes.data, e12.ctypes.data, rows.ctypes.data), None, "ig_grid_bricks_fill")
-            e16 = np.empty((max(nent, 1), 4), dtype=np.uint32)
-            brick_slots = np.zeros(nb, dtype=np.int32)
-            slot_ptr = np.empty(nent + 1, dtype=np.int32)
-            nslots = ctypes.c_int64()
-            _lib.check(b._L.ig_grid_slots_build(nb, ptr.ctypes.data, e12.ctypes.data, rows.ctypes.data, 16 * bm * bs, e16.ctypes.data,
-                                                brick_slots.ctypes.data, slot_ptr.ctypes.data, ctypes.byref(nslots)), None, "ig_grid_slots_build")
-            del e12, rows
-            sptr = np.zeros(nb + 1, dtype=np.int64)
-            np.cumsum(brick_slots, out=sptr[1:])
-            fine = self._format('_support_fine', ncols)
-            nseg = (16 // (fine[1] if fine is not None else 16)) * bm * bs      # segments per brick (the kernel looks up 512 per run)
-            tasks, table, shared = brick_tasks(brick_slots, sptr, chunk, run, max_bricks=min(64, 512 // nseg))
-            words = 4
-            if self._real_weights(data):
-                e16 = np.ascontiguousarray(e16.reshape(-1, 4)[:, [0, 1, 3]])     # {cell, re, row}: 12 bytes per nonzero
-                words = 3
-            self._slots = dict(n0=int(n0), nm=int(nm), bm=int(bm), bs=int(bs), ncols=int(ncols), ntasks=int(tasks.shape[0]), words=words,
-                               nshared=int(shared.size), nslots=int(nslots.value), nentries=nent,
-                               tasks=b.copy_array(tasks.reshape(-1) if tasks.size else np.zeros(4, np.int32), name=self._name + ".slotTasks"),
-                               table=b.copy_array(table.reshape(-1) if table.size else np.zeros(2, np.int32), name=self._name + ".slotTable"),
-                               entries=b.copy_array(e16.reshape(-1), name=self._name + ".slotEntries"),
-                               slot_ptr=b.copy_array(slot_ptr[:int(nslots.value) + 1].copy(), name=self._name + ".slotPtr"),
-                               shared=b.copy_array(shared if shared.size else np.zeros(1, np.int32), name=self._name + ".slotSharedBricks"))
-            self.__dict__.setdefault('_slots_by', {})[int(ncols)] = self._slots
-
-        def set_grid_separable(self, sep):
-            """The matrix in SEPARABLE form (indigo_amd.interp.interp_sep_records: one record per sample, columns numbered in the
-            memory order of the coil-interleaved grid panel): the products with interleaved panels of 2, 4 or 8 columns compute their
-            taps from the records (ig_grid_gather_sep / ig_grid_scatter_sep) instead of streaming the stored ones."""
-            b = self._backend
-            n0, nm, ns = (int(v) for v in sep['dims'])
-            assert sep['records'].shape[0] == self.shape[0] and n0 * nm * ns == self.shape[1]
-            rec = np.ascontiguousarray(sep['records'])
-            # the forward reads the records as they are (16 or 32 words apart: one 64- or 128-byte line each); the share scatter wants every
-            # record followed by room for the sample's panel row -- a second, wider copy that set_grid_shares uploads when it is needed
-            rw = rec.shape[1]
-            self._sep = dict(tw=int(sep['tw']), dims=(n0, nm, ns), gconst=complex(sep['gconst']), host=rec, stride=rw,
-                             records=b.copy_array(rec.reshape(-1), name=self._name + ".sepRecords"))
-
-        def _gather_order(self, ncols):
-            """The order in which the workgroups of the record gather take their groups of consecutive samples (ig_grid_gather_sep's
-            group_order) for an `ncols`-column panel: the groups sorted by the 32^3-cell block of the grid their first sample's first tap
-            lies in, blocks in Morton order -- built once per panel width from the host copy of the records.  Measured
-            (profiles/r06_gather_order.txt): 8 x the spokes 3.28 -> 2.79 ms, half-width 3 1.46 -> 1.36 ms, the headline 0.430 -> 0.416 ms."""
-            sep = self._sep
-            by = sep.setdefault('order', {})
-            if ncols not in by:
-                rec, tw = sep['host'], sep['tw']
-                group = int(self._backend._L.ig_grid_gather_sep_group(int(ncols), int(tw)))
-                by[ncols] = None
-                if group > 0 and rec.shape[0] > 4 * group:
-                    h0, h1 = rec[::group, 3 * tw], rec[::group, 3 * tw + 1]
-                    j = [(h0 & 0xffff).astype(np.int64) >> 5, (h0 >> 16).astype(np.int64) >> 5, (h1 & 0xffff).astype(np.int64) >> 5]
-                    key = np.zeros_like(j[0])
-                    for bit in range(11):                       # axes of up to 65535 points: 11 bits of 32-cell blocks each
-                        for a in range(3):
-                            key |= ((j[a] >> bit) & 1) << (3 * bit + a)
-                    by[ncols] = self._backend.copy_array(np.argsort(key, kind='stable').astype(np.uint32), name=self._name + ".gatherOrder%d" % ncols)
-            return by[ncols]
-
-        def set_grid_shares(self, ncols=8, bm=8, bs=2, chunk=1024, run=1024):
-            """The adjoint of an `ncols`-column interleaved panel as a scatter of SHARES (ig_grid_scatter_sep): every (sample, brick of
-            16 x bm x bs cells) pair the sample's footprint meets is one 8-byte share, binned by brick on the host (ig_grid_shares_count /
-            _fill: brick order, sample order inside a brick); the taps come from the separable records (set_grid_separable, which must
-            come first, as must set_grid_support_fine: a brick's flagged segments are looked up here, once).  A task (one wave) is a run
-            of consecutive non-empty bricks of about `run` shares, or a piece of at most `chunk` shares of a heavy brick (shared)."""
-            b = self._backend
-            sep = getattr(self, '_sep', None)
-            assert sep is not None and ncols in (4, 8)
-            bm, bs = min(int(bm), 4), min(int(bs), 4)          # (the brick image is four MFMA blocks x four accumulator groups)
-            n0, nm, ns = sep['dims']
-            rec, tw = sep['host'], sep['tw']
-            fine = self._format('_support_fine_host', ncols)
-            sup = getattr(self, '_support_host', None)
-            tab, tile, zw = (fine[0], fine[1], getattr(self, '_support_zw', 16)) if fine is not None else \
-                            (sup, 16, getattr(self, '_support_zw', 16)) if sup is not None else (None, 16, 16)
-            by = self.__dict__.setdefault('_shares_by', {})
-            xs = 16 // tile
-            while xs * bm * bs > 64 and bs > 1:
-                bs //= 2
-            while xs * bm * bs > 64 and bm > 1:
-                bm //= 2
-            # (bricks need not divide the middle and slow axes: the part of a last brick outside the grid is never flagged below)
-            nbx, nbm, nbs = n0 // 16, -(-nm // bm), -(-ns // bs)
-            nb = nbx * nbm * nbs
-            counts = np.zeros(nb, dtype=np.int32)
-            if n0 % 16 or b._L.ig_grid_shares_count(rec.shape[0], rec.ctypes.data, tw, n0, nm, ns, bm, bs, counts.ctypes.data) != 0:
-                log.info("%s: no share format; the adjoint keeps the stored-tap routes", self._name)
-                by[int(ncols)] = None
-                return
-            ptr = np.zeros(nb + 1, dtype=np.int64)
-            np.cumsum(counts, out=ptr[1:])
-            assert ptr[-1] < 2**31, "shares are addressed with 32 bits"
-            shares = np.empty((max(int(ptr[-1]), 1), 2), dtype=np.uint32)
-            _lib.check(b._L.ig_grid_shares_fill(rec.shape[0], rec.ctypes.data, tw, n0, nm, ns, bm, bs, ptr.ctypes.data, shares.ctypes.data),
-                       None, "ig_grid_shares_fill")
-            tasks, table, shared = brick_tasks(counts, ptr, int(chunk), int(run), max_bricks=64)
-            # the flagged segments of every non-empty brick: bit xs + XS * (im + bm * is), from the support table's input-side bitmaps
-            bricks = table[:, 0].astype(np.int64) if table.size else np.zeros(0, np.int64)
-            mask = np.zeros(bricks.size, dtype=np.uint64)
-            if bricks.size:
-                bits = None
-                if tab is not None:
-                    nt = n0 // tile
-                    tabh = np.ascontiguousarray(tab, dtype=np.int16).reshape(-1)
-                    off = 2 * (ns * nt + nt)
-                    bits = tabh[off:off + 2 * ns * nt * zw].view(np.uint32).reshape(ns * nt, zw)
-                bx, bmi, bsi = bricks % nbx, (bricks // nbx) % nbm, bricks // (nbx * nbm)
-                for is_ in range(bs):
-                    for im in range(bm):
-                        km, ks = bmi * bm + im, bsi * bs + is_
-                        inside = (km < nm) & (ks < ns)                 # (a last brick may reach beyond the grid)
-                        kmc, ksc = np.minimum(km, nm - 1), np.minimum(ks, ns - 1)
-                        for x in range(xs):
-                            bit = inside.astype(np.uint64) if bits is None else \
-                                (((bits[ksc * nt + bx * xs + x, kmc % zw] >> (kmc // zw).astype(np.uint32)) & np.uint32(1)).astype(np.uint64) * inside)
-                            mask |= bit << np.uint64(x + xs * (im + bm * is_))
-            tab16 = np.empty((max(bricks.size, 1), 4), dtype=np.uint32)
-            if bricks.size:
-                tab16[:, 0:2] = table.astype(np.uint32)
-                tab16[:, 2] = (mask & np.uint64(0xffffffff)).astype(np.uint32)
-                tab16[:, 3] = (mask >> np.uint64(32)).astype(np.uint32)
-            sh_rows = tab16[np.searchsorted(bricks, shared.astype(np.int64))] if shared.size else np.zeros((1, 4), np.uint32)
-            if 'recx' not in sep:
-                # (the MFMA scatter reads a share's record and panel row as ONE line: record, then the row k_sep_pack_recx writes there)
-                rw = rec.shape[1]
-                rs = 32 if rw == 16 else 64
-                recx = np.zeros((rec.shape[0], rs), dtype=np.uint32)
-                recx[:, :rw] = rec
-                sep['recx'] = b.copy_array(recx.reshape(-1), name=self._name + ".sepRecordsWithRows")
-                sep['stride_x'] = rs
-            by[int(ncols)] = dict(bm=int(bm), bs=int(bs), tile=int(tile), ncols=int(ncols), ntasks=int(tasks.shape[0]), nshared=int(shared.size),
-                                  nshares=int(ptr[-1]), nbricks=int(bricks.size),
-                                  tasks=b.copy_array(tasks.reshape(-1) if tasks.size else np.zeros(4, np.int32), name=self._name + ".shareTasks"),
-                                  table=b.copy_array(tab16.reshape(-1), name=self._name + ".shareTable"),
-                                  shares=b.copy_array(shares.reshape(-1), name=self._name + ".shares"),
-                                  shared=b.copy_array(np.ascontiguousarray(sh_rows).reshape(-1), name=self._name + ".shareSharedBricks"))
-
-        def set_grid_dims(self, n0, nm, ns):
-            """Hint: the columns of the matrix are the points of an n0 x nm x ns grid, n0 running fastest (a gridding matrix).
-            The wide adjoint then bins by bricks of 16 x 2 x 2 points instead of 16 consecutive columns."""
-            assert int(n0) * int(nm) * int(ns) == self.shape[1]
-            self._grid_dims = (int(n0), int(nm), int(ns))
-            self._wide = False
-
-        def _guess_grid_dims(self):
-            """(n, n, n) when the column count is a cube with n a multiple of 32, else None.  Only a grouping of the columns:
-            a wrong guess costs speed, never correctness (rows that touch more than 64 bricks decline the format)."""
-            k = self.shape[1]
-            n = int(round(k ** (1.0 / 3.0)))
-            return (n, n, n) if n > 0 and n ** 3 == k and n % 32 == 0 else None
-
-        def _wide_bricks(self):
-            """The matrix binned by bricks, 12-byte entries {column inside the brick, re, im} + their rows: the format of
-            ig_ccsrmm_t_bricks_wide[_grid] (adjoint of a 64-column column-major panel as a scatter).  Bricks are 16 x bm x bs
-            points of the grid the columns form (set_grid_dims, or a cube guessed from the column count; tuning
-            'wide_brick_shape'), else 16 consecutive columns.  Built on first use; None when the matrix does not qualify
-            (a row touching more than 64 bricks)."""
-            wb = getattr(self, '_wide', False)
-            if wb is not False:
-                return wb
-            b = self._backend
-            m, k = self.shape
-            if self._host_csr is not None:
-                indptr, indices, data = self._host_csr.indptr, self._host_csr.indices, self._host_csr.data
-            else:
-                indptr, indices, data = self.rowPtrs.to_host(), self.colInds.to_host(), self.values.to_host()
-            indptr = np.ascontiguousarray(indptr, dtype=np.int32)
-            indices = np.ascontiguousarray(indices, dtype=np.int32)
-            data = np.ascontiguousarray(data, dtype=_C64)
-            dims = getattr(self, '_grid_dims', None) or self._guess_grid_dims()
-            bm, bs = b.tuning.get('wide_brick_shape', (2, 2))
-            geoms = []
-            if dims is not None and bm * bs > 1 and dims[0] % 16 == 0 and dims[1] % bm == 0 and dims[2] % bs == 0:
-                geoms.append((dims[0], dims[1], dims[2], bm, bs))
-            geoms.append((k, 1, 1, 1, 1))
-            for n0, nm, ns, bm, bs in geoms:
-                nbx, nbm = n0 // 16, nm // bm
-                # grid bricks: a row's share of a brick padded to QUADS (one panel row is loaded per four entries)
-                unit = 4 if bm * bs > 1 else 1
-                counts = np.zeros(nbx * nbm * (ns // bs), dtype=np.int32)
-                if b._L.ig_grid_bricks_count(m, indptr.ctypes.data, indices.ctypes.data, n0, nm, ns, bm, bs, unit, counts.ctypes.data) == 0:
-                    # a matrix whose rows do not cluster on the (guessed) grid would be mostly padding in quads: keep 16-row bricks
-                    if unit == 1 or int(counts.sum(dtype=np.int64)) <= 1.6 * max(int(indptr[-1] - indptr[0]), 1):
-                        break
-            else:
-                self._wide = None
-                return None
-            ptr = np.zeros(counts.size + 1, dtype=np.int64)
-            np.cumsum(counts, out=ptr[1:])
-            e12 = np.empty((max(int(ptr[-1]), 1), 3), dtype=np.uint32)
-            rows = np.empty(max(int(ptr[-1]) // unit, 1), dtype=np.uint32)
-            _lib.check(b._L.ig_grid_bricks_fill(m, indptr.ctypes.data, indices.ctypes.data, data.ctypes.data, n0, nm, ns, bm, bs, unit,
-                                                ptr.ctypes.data, e12.ctypes.data, rows.ctypes.data), None, "ig_grid_bricks_fill")
-            if unit > 1 and ptr[-1] > 0:
-                # padding entries (weight zero) take the cell of the real entry before them: whatever the panel row holds
-                # (an infinity times zero) lands on a cell the sample touches anyway
-                cell = e12[:int(ptr[-1]), 0]
-                last_real = np.maximum.accumulate(np.where(cell != 0xffffffff, np.arange(cell.size), 0))
-                cell[:] = cell[last_real]
-            # tasks: pieces of at most 4096 entries of a heavy brick, runs of about 1024 entries of consecutive bricks, longest first.
-            # Measured on BASELINE config 3 and rejected (round 3, profiles/r03_cfg3_sweep_*.txt): bricks in index order or in a
-            # (y, z)-blocked order of the grid, with chunks of 4..64 consecutive workgroups dealt to one XCD so that the bricks that
-            # need the same rows of X meet behind one L2 -- 3.7..4.2 ms against 3.35 ms, and the same 9.7 GB of re-fetched rows by
-            # the PMC counters: a brick takes a wave ~25 us, a line lives ~7 us in a 4 MB L2 that 0.5 TB/s stream through.
-            chunk, run = (max(4, int(v) // 4 * 4) for v in b.tuning.get('wide_task_shape', (8192, 2048)))
-            tasks, table, shared = brick_tasks(counts, ptr, chunk, run, max_bricks=64, longest_first=True)
-            # tiles (16 rows of the result) some task stores in full: those of the non-empty bricks that are not cut into shared pieces
-            owned_b = np.zeros(counts.size, dtype=bool)
-            owned_b[table[:, 0]] = True
-            owned_b[shared] = False
-            ob = np.flatnonzero(owned_b).astype(np.int64)
-            bx, bmi, bsi = ob % nbx, (ob // nbx) % nbm, ob // (nbx * nbm)
-            owned = np.zeros(k // 16, dtype=bool)
-            for im in range(bm):
-                for is_ in range(bs):
-                    owned[bx + nbx * ((bmi * bm + im) + nm * (bsi * bs + is_))] = True
-            bits = np.packbits(np.concatenate([owned, np.zeros((-owned.size) % 32, dtype=bool)]), bitorder='little').view(np.uint32)
-            words = 3
-            if bm * bs > 1 and self._real_weights(data):
-                e12 = np.ascontiguousarray(e12[:, :2])            # {cell, re}: the register-image kernel's real-weight form
-                words = 2
-            self._wide = dict(ntasks=int(tasks.shape[0]), geom=(n0, nm, bm, bs), words=words,
-                              owned=b.copy_array(bits, name=self._name + ".wideOwnedTiles"),
-                              tasks=b.copy_array(tasks.reshape(-1) if tasks.size else np.zeros(4, np.int32), name=self._name + ".wideTasks"),
-                              table=b.copy_array(table.reshape(-1) if table.size else np.zeros(2, np.int32), name=self._name + ".wideTable"),
-                              entries=b.copy_array(e12.reshape(-1), name=self._name + ".wideEntries"),
-                              rows=b.copy_array(rows, name=self._name + ".wideEntryRows"))
-            return self._wide
-
-        def _runs(self, sub):
-            """The run format of the matrix over its touched columns (ig_csr_runs_build; `sub` = the cached (touched columns,
-            compact column indices) pair of the xrows route): built on first use, None when the matrix does not qualify."""
-            r = getattr(self, '_runs_fmt', False)
-            if r is not False:
-                return r
-            b = self._backend
-            m = self.shape[0]
-            indptr = np.ascontiguousarray(self._host_csr.indptr if self._host_csr is not None else self.rowPtrs.to_host(), dtype=np.int32)
-            compact = np.ascontiguousarray(sub[1].to_host(), dtype=np.int32)
-            data = np.ascontiguousarray(self._host_csr.data if self._host_csr is not None else self.values.to_host(), dtype=_C64)
-            nruns = (m + 15) // 16
-            dptr = np.zeros(nruns + 1, dtype=np.int32)
-            K = int(sub[0].size)
-            if indptr[0] != 0 or b._L.ig_csr_runs_build(m, K, indptr.ctypes.data, compact.ctypes.data, data.ctypes.data, dptr.ctypes.data, None, None, None) != 0:
-                log.info("%s: no run format (%s); the forward product keeps the per-nonzero gather", self._name, _lib.last_error(None))
-                self._runs_fmt = None
-                return None
-            dcols = np.empty(max(int(dptr[-1]), 1), dtype=np.uint32)
-            entries = np.empty((max(int(indptr[-1]), 1), 3), dtype=np.uint32)
-            real = ctypes.c_int(0)
-            _lib.check(b._L.ig_csr_runs_build(m, K, indptr.ctypes.data, compact.ctypes.data, data.ctypes.data, dptr.ctypes.data,
-                                              dcols.ctypes.data, entries.ctypes.data, ctypes.byref(real)), None, "ig_csr_runs_build")
-            # order of the runs: by the 16 x 16 x 16 brick of the grid (set_grid_dims, or a cube guessed from the column count) their
-            # first nonzero falls into -- runs that are neighbours in space share panel rows and then meet behind one L2.  Only a
-            # grouping: any order gives the same product.
-            order = None
-            dims = getattr(self, '_grid_dims', None) or self._guess_grid_dims()
-            if dims is not None and b.tuning.get('runs_order', True) and nruns > 1:
-                touched = sub[0].to_host().astype(np.int64)
-                first = np.minimum(indptr[np.minimum(np.arange(nruns, dtype=np.int64) * 16, m - 1)], max(int(indptr[-1]) - 1, 0))
-                col = touched[compact[first]] if indptr[-1] > 0 else np.zeros(nruns, np.int64)
-                n0, nm, ns = dims
-                bx, bm_, bs_ = (col % n0) // 16, ((col // n0) % nm) // 16, (col // (n0 * nm)) // 16
-                key = bx + ((n0 + 15) // 16) * (bm_ + ((nm + 15) // 16) * bs_)
-                order = b.copy_array(np.argsort(key, kind='stable').astype(np.int32), name=self._name + ".runOrder")
-            self._runs_fmt = dict(dptr=b.copy_array(dptr, name=self._name + ".runPtr"), dcols=b.copy_array(dcols, name=self._name + ".runCols"),
-                                  entries=b.copy_array(entries.reshape(-1), name=self._name + ".runEntries"), all_real=int(real.value),
-                                  ndistinct=int(dptr[-1]), order=order)
-            return self._runs_fmt
-
-        def set_row_order(self, perm):
-            """Store the matrix with its rows in the order `perm` (stored row r = row perm[r] of A), e.g. gridding
-            samples sorted by the grid cell they touch: neighbouring rows then gather neighbouring panel rows.
-            The products are unchanged -- the forward result is written through the permutation and the
-            adjoint reads its panel through it."""
-            b = self._backend
-            perm = np.ascontiguousarray(perm, dtype=np.int32)
-            assert self._host_csr is not None and perm.shape == (self.shape[0],)
-            Ap = self._host_csr[perm]
-            Ap.sort_indices()
-            self.rowPtrs = b.copy_array(Ap.indptr.astype(np.int32), name=self._name + ".rowPtrs")
-            self.colInds = b.copy_array(Ap.indices.astype(np.int32), name=self._name + ".colInds")
-            self.values = b.copy_array(Ap.data.astype(_C64), name=self._name + ".data")
-            self._host_csr = Ap
-            self._t = None
-            self._values_re = False          # (built on first use from the reordered values)
-            self._weights_real = None
-            self._perm = b.copy_array(perm, name=self._name + ".rowOrder")
-
-        def _real_weights(self, data):
-            """are the matrix's weights real up to rounding residue (weights_are_real; one pass over the values, remembered) -- and
-            does the backend's tuning allow the 4-byte forms?"""
-            if not self._backend.tuning.get('real_entries', True):
-                return False
-            r = getattr(self, '_weights_real', None)
-            if r is None:
-                r = self._weights_real = weights_are_real(data)
-            return r
-
-        def _real_values(self):
-            """the weights' real parts as a float32 device array when the matrix is real up to rounding residue (built on first
-            use; None otherwise, or when the backend's tuning asks for complex entries)"""
-            r = getattr(self, '_values_re', False)
-            if r is False:
-                r = None
-                data = self._host_csr.data if self._host_csr is not None else self.values.to_host()
-                if self._real_weights(data):
-                    r = self._backend.copy_array(np.ascontiguousarray(data.real, dtype=np.float32), name=self._name + ".dataRe")
-                self._values_re = r
-            return r
-
-        def forward(self, y, x, alpha=1, beta=0):
-            perm = getattr(self, '_perm', None)
-            if getattr(self, '_grid_il', False):
-                assert perm is None and x.contiguous, "interleaved panels: no row order, contiguous grid panel"
-                self._check_panels(y, x, self.values)
-                b = self._backend
-                ar, ai = _cplx(alpha)
-                br, bi = _cplx(beta)
-                m, k = self.shape
-                sep = getattr(self, '_sep', None)
-                if sep is not None and x.shape[1] in (2, 4, 8) and b.tuning.get('sep_gather', True):
-                    # the taps computed from one 64-byte record per sample (ig_grid_gather_sep): no index or value stream
-                    gr, gi = _cplx(complex(alpha) * sep['gconst'])
-                    n0, nm, ns = sep['dims']
-                    order = self._gather_order(x.shape[1]) if b.tuning.get('gather_order', True) else None
-                    b._check(b._L.ig_grid_gather_sep(b._ctx, m, x.shape[1], sep['tw'], ctypes.c_void_p(sep['records']._arr), sep['stride'], ctypes.c_void_p(x._arr),
-                                                     n0, nm, ns, gr, gi, br, bi, ctypes.c_void_p(y._arr), y._leading_dim,
-                                                     ctypes.c_void_p(order._arr) if order is not None else None), "ig_grid_gather_sep")
-                    return
-                vre = self._real_values() if x.shape[1] in (2, 4, 8) else None
-                if vre is not None:
-                    # every weight real (see weights_are_real): the gather reads 4-byte values
-                    b._check(b._L.ig_ccsrmm_il_rw(b._ctx, m, k, x.shape[1], self.values.size, ar, ai,
-                                                  ctypes.c_void_p(self.values._arr), ctypes.c_void_p(vre._arr), ctypes.c_void_p(self.colInds._arr),
-                                                  ctypes.c_void_p(self.rowPtrs._arr), ctypes.c_void_p(x._arr), br, bi,
-                                                  ctypes.c_void_p(y._arr), y._leading_dim), "ig_ccsrmm_il_rw")
-                    return
-                b._check(b._L.ig_ccsrmm_il(b._ctx, m, k, x.shape[1], self.values.size, ar, ai,
-                                           ctypes.c_void_p(self.values._arr), ctypes.c_void_p(self.colInds._arr),
-                                           ctypes.c_void_p(self.rowPtrs._arr), ctypes.c_void_p(x._arr), br, bi,
-                                           ctypes.c_void_p(y._arr), y._leading_dim), "ig_ccsrmm_il")
-                return
-            if perm is None and 16 <= x.shape[1] <= 64 and self._col_frac <= 0.6 \
-                    and self.values.size >= self.shape[1] and self._backend.tuning['xrows']:
-                # a wide panel of which the matrix touches a fraction of the rows (a gridding matrix: 30 % of its grid):
-                # the panel is repacked row-major anyway -- repack only the touched rows (ig_ccsrmm_xrows)
-                self._check_panels(y, x, self.values)
-                b = self._backend
-                sub = getattr(self, '_xrows', None)
-                if sub is None:
-                    indices = self._host_csr.indices if self._host_csr is not None else self.colInds.to_host()
-                    mark = np.zeros(self.shape[1], dtype=bool)
-                    mark[indices] = True
-                    touched = np.flatnonzero(mark).astype(np.int32)
-                    compact = np.searchsorted(touched, indices).astype(np.int32)
-                    sub = self._xrows = (b.copy_array(touched, name=self._name + ".touchedCols"),
-                                         b.copy_array(compact, name=self._name + ".compactColInds"))
-                ar, ai = _cplx(alpha)
-                br, bi = _cplx(beta)
-                m, k = self.shape
-                runs = self._runs(sub) if (x.shape[1] == 64 and b.tuning.get('runs', True) and sub[0].size * 512 < 2 ** 32) else None
-                if runs is not None:
-                    # 64 columns: the run format -- every panel row a run of 16 matrix rows touches is loaded once (ig_ccsrmm_xrows_runs)
-                    b._check(b._L.ig_ccsrmm_xrows_runs(b._ctx, m, k, self.values.size, ar, ai, ctypes.c_void_p(self.rowPtrs._arr),
-                                                       ctypes.c_void_p(runs['dptr']._arr), ctypes.c_void_p(runs['dcols']._arr),
-                                                       ctypes.c_void_p(runs['entries']._arr), runs['all_real'],
-                                                       ctypes.c_void_p(runs['order']._arr) if runs['order'] is not None else None,
-                                                       ctypes.c_void_p(x._arr), x._leading_dim, br, bi, ctypes.c_void_p(y._arr), y._leading_dim,
-                                                       ctypes.c_void_p(sub[0]._arr), sub[0].size), "ig_ccsrmm_xrows_runs")
-                    return
-                b._check(b._L.ig_ccsrmm_xrows(b._ctx, m, k, x.shape[1], self.values.size, ar, ai,
-                                              ctypes.c_void_p(self.values._arr), ctypes.c_void_p(sub[1]._arr),
-                                              ctypes.c_void_p(self.rowPtrs._arr), ctypes.c_void_p(x._arr), x._leading_dim,
-                                              br, bi, ctypes.c_void_p(y._arr), y._leading_dim,
-                                              ctypes.c_void_p(sub[0]._arr), sub[0].size), "ig_ccsrmm_xrows")
-                return
-            if perm is None:
-                return super().forward(y, x, alpha=alpha, beta=beta)
-            self._check_panels(y, x, self.values)
-            b = self._backend
-            ar, ai = _cplx(alpha)
-            br, bi = _cplx(beta)
-            m, k = self.shape
-            b._check(b._L.ig_ccsrmm_rowperm(b._ctx, m, k, x.shape[1], self.values.size, ar, ai,
-                                            ctypes.c_void_p(self.values._arr), ctypes.c_void_p(self.colInds._arr),
-                                            ctypes.c_void_p(self.rowPtrs._arr),
-                                            ctypes.c_void_p(x._arr), x._leading_dim, br, bi,
-                                            ctypes.c_void_p(y._arr), y._leading_dim,
-                                            ctypes.c_void_p(perm._arr)), "ig_ccsrmm_rowperm")
-
-        def adjoint(self, y, x, alpha=1, beta=0):
-            self._check_panels(y, x, self.values)
-            b = self._backend
-            sup = getattr(self, '_support', None)
-            perm = getattr(self, '_perm', None)
-            shf = self._format('_shares', x.shape[1], exact=True)
-            if (shf is not None and perm is None and beta == 0 and y.contiguous and getattr(self, '_grid_il', False) and shf['ntasks'] > 0
-                    and b.tuning.get('sep_scatter', True)):
-                sep = self._sep
-                if not (self._format('_support_fine', x.shape[1]) is not None or sup is not None):
-                    y._zero()           # without a support table every row is defined: bricks no sample touches stay zero
-                ar, ai = _cplx(complex(alpha) * np.conj(sep['gconst']))
-                n0, nm, ns = sep['dims']
-                b._check(b._L.ig_grid_scatter_sep(b._ctx, self.shape[0], x.shape[1], sep['tw'], ctypes.c_void_p(sep['recx']._arr), sep['stride_x'],
-                                                  ctypes.c_void_p(shf['shares']._arr), ctypes.c_void_p(x._arr), x._leading_dim, ctypes.c_void_p(y._arr),
-                                                  n0, nm, ns, shf['bm'], shf['bs'], ctypes.c_void_p(shf['tasks']._arr), shf['ntasks'],
-                                                  ctypes.c_void_p(shf['table']._arr), ctypes.c_void_p(shf['shared']._arr), shf['nshared'], shf['tile'], ar, ai),
-                         "ig_grid_scatter_sep")
-                return
-            br = self._format('_bricks', x.shape[1], exact=True)
-            # (the gather routes over the transposed matrix read 16-word bitmaps only: with another table they compute every
-            # row -- a superset of what any reader of the grid looks at)
-            sup_gather = sup if getattr(self, '_support_zw', 16) == 16 else None
-            if (br is not None and perm is None and beta == 0 and y.contiguous and getattr(self, '_grid_il', False)
-                    and x.shape[1] == br['ncols']):
-                fine = self._format('_support_fine', x.shape[1])
-                tab, tile = (fine[0], fine[1]) if fine is not None else (sup[0] if sup is not None else None, 16)
-                if tab is None:
-                    y._zero()           # without a support table every row is defined: bricks no sample touches stay zero
-                ar, ai = _cplx(alpha)
-                m, k = self.shape
-                b._check(b._L.ig_ccsrmm_t_bricks(b._ctx, m, k, x.shape[1], ar, ai,
-                                                 ctypes.c_void_p(br['entries']._arr), ctypes.c_void_p(br['rounds']._arr), ctypes.c_void_p(x._arr), x._leading_dim,
-                                                 ctypes.c_void_p(y._arr), ctypes.c_void_p(tab._arr) if tab is not None else None,
-                                                 br['n0'], br['nm'], br['bm'], br['bs'], ctypes.c_void_p(br['tasks']._arr), br['ntasks'],
-                                                 ctypes.c_void_p(br['table']._arr), ctypes.c_void_p(br['shared']._arr), br['nshared'], tile,
-                                                 getattr(self, '_support_zw', 16), br['words']),
-                         "ig_ccsrmm_t_bricks")
-                return
-            sl = self._format('_slots', x.shape[1], exact=True)
-            if sl is not None and perm is None and beta == 0 and y.contiguous and x.shape[1] == sl['ncols'] and sl['ntasks'] > 0:
-                fine = self._format('_support_fine', x.shape[1])
-                tab, tile = (fine[0], fine[1]) if fine is not None else (sup[0] if sup is not None else None, 16)
-                if tab is None:
-                    y._zero()
-                ar, ai = _cplx(alpha)
-                m, k = self.shape
-                b._check(b._L.ig_ccsrmm_t_slots(b._ctx, m, k, x.shape[1], ar, ai, ctypes.c_void_p(sl['entries']._arr), ctypes.c_void_p(sl['slot_ptr']._arr),
-                                                ctypes.c_void_p(x._arr), x._leading_dim, ctypes.c_void_p(y._arr),
-                                                ctypes.c_void_p(tab._arr) if tab is not None else None, sl['n0'], sl['nm'], sl['bm'], sl['bs'],
-                                                ctypes.c_void_p(sl['tasks']._arr), sl['ntasks'], ctypes.c_void_p(sl['table']._arr),
-                                                ctypes.c_void_p(sl['shared']._arr), sl['nshared'], tile, getattr(self, '_support_zw', 16), sl['words']),
-                         "ig_ccsrmm_t_slots")
-                return
-            if (x.shape[1] == 64 and beta == 0 and perm is None and not getattr(self, '_grid_il', False) and self.shape[1] % 16 == 0
-                    and self.shape[1] > 0 and self.shape[0] * 512 < 2 ** 31 and self.values.size >= self.shape[1] // 4
-                    and b.tuning['wide_bricks']):
-                # 64 columns at the reference boundary (BASELINE config 3): scatter through LDS brick images
-                wb = self._wide_bricks()
-                if wb is not None:
-                    ar, ai = _cplx(alpha)
-                    m, k = self.shape
-                    n0, nm, bm, bs = wb['geom']
-                    b._check(b._L.ig_ccsrmm_t_bricks_wide_grid(b._ctx, m, k, ar, ai, ctypes.c_void_p(wb['entries']._arr), ctypes.c_void_p(wb['rows']._arr),
-                                                               ctypes.c_void_p(x._arr), x._leading_dim, ctypes.c_void_p(y._arr), y._leading_dim,
-                                                               ctypes.c_void_p(wb['tasks']._arr), wb['ntasks'], ctypes.c_void_p(wb['table']._arr),
-                                                               ctypes.c_void_p(wb['owned']._arr), n0, nm, bm, bs, wb['words']),
-                             "ig_ccsrmm_t_bricks_wide_grid")
-                    return
-            if getattr(self, '_grid_il', False):
-                assert perm is None and beta == 0 and y.contiguous, "interleaved panels: no row order, beta = 0"
-                pt, it, dt = self._transposed()
-                tab, n0, nm = sup_gather if sup_gather is not None else (None, 0, 0)
-                ar, ai = _cplx(alpha)
-                m, k = self.shape
-                b._check(b._L.ig_ccsrmm_t_grid_il(b._ctx, m, k, x.shape[1], dt.size, ar, ai,
-                                                  ctypes.c_void_p(dt._arr), ctypes.c_void_p(it._arr), ctypes.c_void_p(pt._arr),
-                                                  ctypes.c_void_p(x._arr), x._leading_dim, ctypes.c_void_p(y._arr),
-                                                  ctypes.c_void_p(tab._arr) if tab is not None else None, n0, nm),
-                         "ig_ccsrmm_t_grid_il")
-                return
-            if perm is not None:
-                assert not self._exwrite and b.adjoint_policy == 'transpose' and x.shape[1] <= 8, \
-                    "row-ordered matrices use the packed transposed gather"
-            if (sup_gather is not None or perm is not None) and not self._exwrite and b.adjoint_policy == 'transpose':
-                pt, it, dt = self._transposed()
-                b.ccsrmm_t(y, self.shape, it, pt, dt, x, alpha=alpha, beta=beta, support=sup_gather, xperm=perm)
-                return
-            if self._exwrite or b.adjoint_policy != 'transpose':
-                b.ccsrmm(y, self.shape, self.colInds, self.rowPtrs, self.values,
-                         x, alpha=alpha, beta=beta, adjoint=True, exwrite=self._exwrite)
-            else:
-                pt, it, dt = self._transposed()
-                b.ccsrmm_t(y, self.shape, it, pt, dt, x, alpha=alpha, beta=beta)
+HipBackend.csr_matrix = _csr_matrix

@@ -125,6 +125,17 @@ def observed_route(A, tuning):
                 sep=None if sep is None else (sep['tw'], 'g=1' if sep['gconst'] == 1 else 'g!=1'), fwd=fwd, adj=adj)
 
 
+def check_route_queries(A, observed):
+    """the matrix's own answer (forward_route / adjoint_route) agrees with the restatement above, for every chunk width"""
+    import types
+    M = _leaves(_trees(A)[0])[0]._get_or_create_device_matrix()
+    y = types.SimpleNamespace(contiguous=True)
+    for w in observed['widths']:
+        assert M.forward_route(w) == {'sep': 'sep', 'sep-unordered': 'sep', 'rw': 'il_rw', 'il': 'il'}[observed['fwd']], (w, observed)
+        assert M.adjoint_route(w, 0, y) == {'shares': 'shares', 'bricks': 'bricks', 'slots': 'slots', 'gather': 'gather_il'}[observed['adj'][w].rstrip('234')], \
+            (w, observed)
+
+
 def _route(widths, sep, fwd, adj, kshift=None, support=None):
     return dict(widths=tuple(widths), kshift=kshift, support=support, sep=sep, fwd=fwd, adj=adj)
 
@@ -210,6 +221,7 @@ def test_route_against_float64(hip, case):
     p = _problem(name)[0]
     A = _with_tuning(hip, tuning, lambda: p.build_zpadfft(hip, coils=list(coils)))
     assert _with_tuning(hip, tuning, lambda: observed_route(A, hip.tuning)) == expect
+    _with_tuning(hip, tuning, lambda: check_route_queries(A, expect))
     err = _with_tuning(hip, tuning, lambda: check_products(hip, A, name, list(coils)))
     print("route %s: worst rel. error %.2e" % (_case_id(case), err))
 
@@ -238,6 +250,7 @@ def test_tuning_switches_on_one_problem(hip, order):
     for tuning, support, expect in seq:
         A = _with_tuning(hip, tuning, lambda: p.build_zpadfft(hip, coils=[0, 1, 2, 3], support=support))
         assert _with_tuning(hip, tuning, lambda: observed_route(A, hip.tuning)) == expect, (tuning, support)
+        _with_tuning(hip, tuning, lambda: check_route_queries(A, expect))
         err = _with_tuning(hip, tuning, lambda: check_products(hip, A, 'chirp', [0, 1, 2, 3]))
         print("tuning %s support=%s: worst rel. error %.2e" % (tuning, support, err))
         del A
