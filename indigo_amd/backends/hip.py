@@ -723,6 +723,11 @@ class HipBackend(Backend):
     def _fft_padded_workspace(self, grid, box_lo, box_dims, batch, layout=0):
         return self._padded_plan(grid, box_lo, box_dims, batch, layout)[1]
 
+    @staticmethod
+    def _slab(slab):
+        """'z' or (z0, z1) -> the (phase, z0, z1) of the ig_fft_exec_cropped*_slab calls"""
+        return (0, 0, 0) if slab == 'z' else (1, int(slab[0]), int(slab[1]))
+
     def fft_padded(self, y, x, w, grid, box_lo, box_dims, workspace=None, layout=0, support=None, support_tile=16, kshift=None):
         C = y.shape[1]
         assert y.dtype == _C64 and x.dtype == _C64 and y.contiguous and x.contiguous
@@ -730,12 +735,7 @@ class HipBackend(Backend):
         assert w is None or (w.contiguous and w.size == x.size * C)
         plan, ws = self._padded_plan(grid, box_lo, box_dims, C, layout, support_tile, kshift)
         assert layout == 0 or (workspace is not None and workspace.nbytes >= ws)
-        self._check(self._L.ig_fft_exec_padded(plan, ctypes.c_void_p(x._arr), 0,
-                                               ctypes.c_void_p(w._arr) if w is not None else None,
-                                               ctypes.c_void_p(y._arr),
-                                               ctypes.c_void_p(workspace._arr) if workspace is not None else None,
-                                               ctypes.c_void_p(support._arr) if support is not None else None),
-                    "ig_fft_exec_padded")
+        self._check(self._L.ig_fft_exec_padded(plan, _ptr(x), 0, _ptr(w), _ptr(y), _ptr(workspace), _ptr(support)), "ig_fft_exec_padded")
 
     def ifft_cropped(self, xc, y, w, grid, box_lo, box_dims, workspace, layout=0, support=None, support_tile=16, slab=None, kshift=None):
         """xc[:, c] = conj(w[:, c]) * crop(IFFT(y[:, c])).  slab (grid layout 1 only): 'z' = only the z pass; (z0, z1) = the y and x
@@ -748,18 +748,10 @@ class HipBackend(Backend):
         assert workspace.nbytes >= ws
         if slab is not None:
             assert layout == 1
-            phase, z0, z1 = (0, 0, 0) if slab == 'z' else (1, int(slab[0]), int(slab[1]))
-            self._check(self._L.ig_fft_exec_cropped_slab(plan, ctypes.c_void_p(y._arr), ctypes.c_void_p(w._arr) if w is not None else None,
-                                                         ctypes.c_void_p(xc._arr), xc.shape[0], ctypes.c_void_p(workspace._arr),
-                                                         ctypes.c_void_p(support._arr) if support is not None else None, phase, z0, z1),
+            self._check(self._L.ig_fft_exec_cropped_slab(plan, _ptr(y), _ptr(w), _ptr(xc), xc.shape[0], _ptr(workspace), _ptr(support), *self._slab(slab)),
                         "ig_fft_exec_cropped_slab")
             return
-        self._check(self._L.ig_fft_exec_cropped(plan, ctypes.c_void_p(y._arr),
-                                                ctypes.c_void_p(w._arr) if w is not None else None,
-                                                ctypes.c_void_p(xc._arr), xc.shape[0],
-                                                ctypes.c_void_p(workspace._arr),
-                                                ctypes.c_void_p(support._arr) if support is not None else None),
-                    "ig_fft_exec_cropped")
+        self._check(self._L.ig_fft_exec_cropped(plan, _ptr(y), _ptr(w), _ptr(xc), xc.shape[0], _ptr(workspace), _ptr(support)), "ig_fft_exec_cropped")
 
     def ifft_cropped_sum(self, x, y, w, grid, box_lo, box_dims, workspace, support=None, slab=None, support_tile=16, kshift=None):
         """x = sum_c conj(w[:, c]) * crop(IFFT(y[:, c])) for a coil-interleaved grid panel y (layout 2): the cropped
@@ -771,16 +763,11 @@ class HipBackend(Backend):
         assert x.size == int(np.prod(box_dims))
         plan, ws = self._padded_plan(grid, box_lo, box_dims, C, 2, support_tile, kshift)
         assert workspace.nbytes >= ws
-        sup = ctypes.c_void_p(support._arr) if support is not None else None
         if slab is None:
-            self._check(self._L.ig_fft_exec_cropped_sum(plan, ctypes.c_void_p(y._arr), ctypes.c_void_p(w._arr),
-                                                        ctypes.c_void_p(x._arr), ctypes.c_void_p(workspace._arr), sup),
-                        "ig_fft_exec_cropped_sum")
+            self._check(self._L.ig_fft_exec_cropped_sum(plan, _ptr(y), _ptr(w), _ptr(x), _ptr(workspace), _ptr(support)), "ig_fft_exec_cropped_sum")
             return
-        phase, z0, z1 = (0, 0, 0) if slab == 'z' else (1, int(slab[0]), int(slab[1]))
-        self._check(self._L.ig_fft_exec_cropped_sum_slab(plan, ctypes.c_void_p(y._arr), ctypes.c_void_p(w._arr),
-                                                         ctypes.c_void_p(x._arr), ctypes.c_void_p(workspace._arr), sup,
-                                                         phase, z0, z1), "ig_fft_exec_cropped_sum_slab")
+        self._check(self._L.ig_fft_exec_cropped_sum_slab(plan, _ptr(y), _ptr(w), _ptr(x), _ptr(workspace), _ptr(support), *self._slab(slab)),
+                    "ig_fft_exec_cropped_sum_slab")
 
     def sum_columns(self, y, X, alpha=1, beta=0, interleaved=False):
         assert y.dtype == _C64 and X.dtype == _C64 and y.contiguous and y.size == X.shape[0]
@@ -978,6 +965,6 @@ class HipBackend(Backend):
 
 
 # the device CSR matrix and the formats of a gridding matrix: backends/hip_csr.py (it needs nothing of this module)
-from indigo_amd.backends.hip_csr import csr_matrix as _csr_matrix       # noqa: E402
+from indigo_amd.backends.hip_csr import _ptr, csr_matrix as _csr_matrix       # noqa: E402
 
 HipBackend.csr_matrix = _csr_matrix

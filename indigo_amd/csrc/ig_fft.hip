@@ -37,6 +37,7 @@
 #include "ig_packed.h"
 #include "ig_fft_ab.h"
 #include "ig_fft_ab_list.h"
+#include <array>
 #include <vector>
 #include <functional>
 #include <algorithm>
@@ -1242,6 +1243,22 @@ static dim3 pass_grid(PassDesc& d, int64_t tpr) {
     return d.grid3 ? dim3((unsigned)tpr, (unsigned)d.ext1, (unsigned)ext2) : dim3((unsigned)(tpr * rows));
 }
 
+// The tiles of a pass at cpt columns (k0 values) each: the launch grid, after checking that the tile count fits and that every
+// in-tile byte offset -- `reach` element steps along the transform axis plus the tile's 16 lanes -- stays inside the 2 GB
+// descriptor window (the weights' too where the pass addresses them)
+static int pass_tiles(ig_ctx* ctx, PassDesc& d, int64_t cpt, int64_t reach, bool weights, const char* kernel, dim3& grid) {
+    const int64_t tpr = (d.ext0 + cpt - 1) / cpt;
+    const int64_t blocks = tpr * (d.ncols / d.ext0);           // ncols = ext0 * ext1 * ext2
+    IG_REQUIRE(ctx, blocks <= 0x7fffffffLL && d.ext1 <= 0x7fffffffLL, "ig_fft: too many tiles");
+    grid = pass_grid(d, tpr);
+    const int64_t lim = 0x7fffffffLL / 8;
+    const int64_t span_in = reach * d.in_sj + 15 * d.in_s[0] + 15 * d.in_sa, span_out = reach * d.out_sj + 15 * d.out_s[0] + 15 * d.out_sa;
+    const int64_t span_w = weights ? reach * d.w_sj + 15 * d.w_s[0] + 15 * d.w_sa : 0;
+    IG_REQUIRE(ctx, d.in_sj >= 0 && d.out_sj >= 0 && d.in_s[0] >= 0 && d.out_s[0] >= 0 && span_in < lim && span_out < lim && span_w < lim,
+               "ig_fft: axis stride too large for the %s kernel", kernel);
+    return IG_OK;
+}
+
 // launch one 2-stage axis pass (n in {256, 512}); axis0 selects the lane mapping for contiguous columns
 int launch_2stage(ig_ctx* ctx, const AxisPlan& ax, const PassDesc& d_in, bool axis0, int wmode) {
     PassDesc d = d_in;
@@ -1249,20 +1266,10 @@ int launch_2stage(ig_ctx* ctx, const AxisPlan& ax, const PassDesc& d_in, bool ax
     IG_REQUIRE(ctx, !d.tile_bits || d.tile_words == 16 || d.tile_words == 0, "ig_fft: the two-stage kernel reads support bitmaps of 16 words per entry (got %d)", d.tile_words);
     const int64_t cpt = (!axis0 && d.cw) ? ax.W / d.cw : ax.W;           // columns (k0 values) per tile
     IG_REQUIRE(ctx, !d.cw || (!axis0 && d.cw <= ax.W && ax.W % d.cw == 0), "ig_fft: bad lane split");
-    const int64_t tpr = (d.ext0 + cpt - 1) / cpt;
-    const int64_t blocks = tpr * (d.ncols / d.ext0);           // ncols = ext0 * ext1 * ext2
-    IG_REQUIRE(ctx, blocks <= 0x7fffffffLL && d.ext1 <= 0x7fffffffLL, "ig_fft: too many tiles");
-    const dim3 grid = pass_grid(d, tpr);
-    {   // every in-tile byte offset must stay inside the 2 GB descriptor window
-        const int64_t lim = 0x7fffffffLL / 8;
-        // (strided passes re-base once per 4 groups of 16 elements and reach the three groups in between through the scalar
-        // offset -- at 32 elements per step on the output side of a 512-point axis: 3 * 32 + 15 element steps plus the tile's lanes must fit)
-        const int64_t reach = axis0 ? ax.n + 15 : 3 * (ax.n / 16) + 15;
-        const int64_t span_in = reach * d.in_sj + 15 * d.in_s[0] + 15 * d.in_sa, span_out = reach * d.out_sj + 15 * d.out_s[0] + 15 * d.out_sa;
-        const int64_t span_w = wmode ? reach * d.w_sj + 15 * d.w_s[0] + 15 * d.w_sa : 0;
-        IG_REQUIRE(ctx, d.in_sj >= 0 && d.out_sj >= 0 && d.in_s[0] >= 0 && d.out_s[0] >= 0 && span_in < lim && span_out < lim && span_w < lim,
-                   "ig_fft: axis stride too large for the two-stage kernel");
-    }
+    // (strided passes re-base once per 4 groups of 16 elements and reach the three groups in between through the scalar
+    // offset -- at 32 elements per step on the output side of a 512-point axis: 3 * 32 + 15 element steps plus the tile's lanes must fit)
+    dim3 grid;
+    if (int rc = pass_tiles(ctx, d, cpt, axis0 ? ax.n + 15 : 3 * (ax.n / 16) + 15, wmode != 0, "two-stage", grid)) return rc;
     const dim3 block((unsigned)(ax.W * ax.T));
 #define IG_2S(R1_, AX0_, WM_, BX_, HF_)                                                             \
     hipLaunchKernelGGL((k_fft_2stage<R1_, 16, 16, 16, AX0_, WM_, BX_, HF_>), grid, block, ax.lds_bytes, ctx->stream, d, ax.d_tw)
@@ -1354,17 +1361,8 @@ int launch_ab_desc(ig_ctx* ctx, const AxisPlan& ax, const PassDesc& d_in, int wm
     IG_REQUIRE(ctx, !d.tile_bits || d.tile_words == (d.tile_range_mode == 1 ? ax.ab_A : ax.ab_B), "ig_fft: the support bitmap has %d words per entry, this pass needs %d",
                d.tile_words, d.tile_range_mode == 1 ? ax.ab_A : ax.ab_B);
     const int64_t cpt = d.cw ? anyfft::AB_W / d.cw : anyfft::AB_W;
-    const int64_t tpr = (d.ext0 + cpt - 1) / cpt;
-    const int64_t blocks = tpr * (d.ncols / d.ext0);
-    IG_REQUIRE(ctx, blocks <= 0x7fffffffLL && d.ext1 <= 0x7fffffffLL, "ig_fft: too many tiles");
-    const dim3 grid = pass_grid(d, tpr);
-    {   // a thread's lane offset reaches (B - 1) element steps + the tile's lanes: inside the 2 GB descriptor window
-        const int64_t lim = 0x7fffffffLL / 8, reach = ax.ab_B - 1;
-        const int64_t span_in = reach * d.in_sj + 15 * d.in_s[0] + 15 * d.in_sa, span_out = reach * d.out_sj + 15 * d.out_s[0] + 15 * d.out_sa;
-        const int64_t span_w = wmode ? reach * d.w_sj + 15 * d.w_s[0] + 15 * d.w_sa : 0;
-        IG_REQUIRE(ctx, d.in_sj >= 0 && d.out_sj >= 0 && d.in_s[0] >= 0 && d.out_s[0] >= 0 && span_in < lim && span_out < lim && span_w < lim,
-                   "ig_fft: axis stride too large for the two-stage kernel");
-    }
+    dim3 grid;      // (a thread's lane offset reaches B - 1 element steps)
+    if (int rc = pass_tiles(ctx, d, cpt, ax.ab_B - 1, wmode != 0, "two-stage", grid)) return rc;
     int wm = wmode;
     if (wmode == 3) {
         IG_REQUIRE(ctx, d.cw == 2 || d.cw == 4 || d.cw == 8 || d.cw == 16, "ig_fft: the coil-summing A x B pass takes 2, 4, 8 or 16 interleaved coils");
@@ -1525,15 +1523,8 @@ int launch_chirp_desc(ig_ctx* ctx, const AxisPlan& ax, const PassDesc& d_in) {
     const int dir = d.inverse ? 1 : 0;
     d.w = ch.d_b[dir]; d.w2 = ch.d_hat_out[dir]; d.chirp_out = 0;
     if (ch.shift) { d.w = ch.d_in_s[dir]; d.w2 = ch.d_hat_out_s[dir]; d.chirp_out = 1; }
-    const int64_t tpr = (d.ext0 + anyfft::AB_W - 1) / anyfft::AB_W;
-    const int64_t blocks = tpr * (d.ncols / d.ext0);
-    IG_REQUIRE(ctx, blocks <= 0x7fffffffLL && d.ext1 <= 0x7fffffffLL, "ig_fft: too many tiles");
-    const dim3 grid = pass_grid(d, tpr);
-    {
-        const int64_t lim = 0x7fffffffLL / 8, reach = ch.sub.ab_B - 1;
-        IG_REQUIRE(ctx, d.in_sj >= 0 && d.out_sj >= 0 && d.in_s[0] >= 0 && d.out_s[0] >= 0 && reach * d.in_sj + 15 * d.in_s[0] < lim && reach * d.out_sj + 15 * d.out_s[0] < lim,
-                   "ig_fft: axis stride too large for the chirp-z kernel");
-    }
+    dim3 grid;
+    if (int rc = pass_tiles(ctx, d, anyfft::AB_W, ch.sub.ab_B - 1, false, "chirp-z", grid)) return rc;
     const dim3 block((unsigned)(anyfft::AB_W * ch.sub.ab_B));
     int r = ig_abz_launch_part0(ctx->stream, ch.m, grid, block, d, ch.sub.d_tw);
     if (!r) r = ig_abz_launch_part1(ctx->stream, ch.m, grid, block, d, ch.sub.d_tw);
@@ -1834,223 +1825,193 @@ int ig_fft_plan_padded(ig_ctx* ctx, const int64_t* dims, const int64_t* box_lo, 
     return IG_OK;
 }
 
-// Grid layout 1 stores the grid as (x, z, y): the element (kx, ky, kz) of batch member c lives at
+// ---- the geometry of a zero-padded plan: the ONE place where a grid layout is defined --------------------------------------
+// Three kinds of memory take part, each described by the element strides of (x, y, z, coil):
+//   image   the compact b0 x b1 x b2 box the padded transform reads and the cropped one writes, and the weights w beside it
+//   mid     what the x and y passes exchange: n0 x b1 x b2, full along x only
+//   grid    the oversampled grid n0 x n1 x n2.  The cropped z pass writes a second array of this shape (the head of the
+//           workspace: its input stays intact), the padded one works in place.
+// Layout 0 stores the grid as (x, y, z) and has no compact intermediate: mid is the full-size array itself seen through the
+// box, i.e. the grid's strides from the offset of the box's (y, z) corner.
+// Layout 1 stores the grid as (x, z, y): the element (kx, ky, kz) of batch member c lives at
 // kx + n0*kz + n0*n2*ky + vol*c.  With it the z pass -- the largest one, the whole grid -- runs at a
 // 4 KB stride on both sides, and the only 2 MB-stride traffic left is the y pass's output (forward) or
 // input (inverse), half a grid.  The y pass reads (writes) its other side from a compact
-// n0 x b1 x b2 array in the workspace.  Whoever consumes the grid must index it the same way
+// n0 x b1 x b2 array in the workspace, behind the full-size part.  Whoever consumes the grid must index it the same way
 // (SenseProblem.fused_interp(layout=1) permutes the gridding matrix's columns).
-static int exec_padded_layout1(ig_fft* p, const float2* x, int64_t x_bstride, const float2* w, float2* y, float2* work,
-                               const short2* support) {
-    ig_ctx* ctx = p->ctx;
-    const int64_t n0 = p->dims[0], n1 = p->dims[1], n2 = p->dims[2];
-    const int64_t b0 = p->box_dims[0], b1 = p->box_dims[1], b2 = p->box_dims[2];
-    const int64_t l0 = p->box_lo[0], l1 = p->box_lo[1], l2 = p->box_lo[2];
-    const int64_t vol = n0 * n1 * n2, bvol = b0 * b1 * b2, C = p->batch;
-    const int64_t cvol = n0 * b1 * b2;                 // compact intermediate per batch member
-    float2* L1 = work + (size_t)p->total;              // behind the full-size part of the workspace
-    {   // pass x: compact weighted image rows -> compact [kx][y'][z']
-        ig_prof_scope prof(ctx, "fft_pad_x", (double)(bvol + (w ? bvol : 0) + cvol) * C * 8.0);
-        PassDesc d{};
-        d.in = x - l0; d.in_sj = 1; d.in_s[0] = b0; d.in_s[1] = b0 * b1; d.in_s[2] = x_bstride;
-        d.w = w ? w - l0 : nullptr; d.w_sj = 1; d.w_s[0] = b0; d.w_s[1] = b0 * b1; d.w_s[2] = bvol;
-        d.out = L1; d.out_sj = 1; d.out_s[0] = n0; d.out_s[1] = n0 * b1; d.out_s[2] = cvol;
-        d.ext0 = b1; d.ext1 = b2; d.ncols = b1 * b2 * C;
-        d.in_lo = (int)l0; d.in_hi = (int)(l0 + b0); d.out_lo = 0; d.out_hi = (int)n0; d.inverse = 0;
-        if (int rc = launch_2stage(ctx, p->axis[0], d, true, w ? 1 : 0)) return rc;
-    }
-    {   // pass y: columns (kx, z'), compact in (4 KB stride), grid out at z = l2 + z' (stride n0*n2)
-        ig_prof_scope prof(ctx, "fft_pad_y", (double)(cvol + n0 * n1 * b2) * C * 8.0);
-        PassDesc d{};
-        d.in = L1 - l1 * n0; d.in_sj = n0; d.in_s[0] = 1; d.in_s[1] = n0 * b1; d.in_s[2] = cvol;
-        d.out = y + l2 * n0; d.out_sj = n0 * n2; d.out_s[0] = 1; d.out_s[1] = n0; d.out_s[2] = vol;
-        d.ext0 = n0; d.ext1 = b2; d.ncols = n0 * b2 * C;
-        d.in_lo = (int)l1; d.in_hi = (int)(l1 + b1); d.out_lo = 0; d.out_hi = (int)n1; d.inverse = 0;
-        // ky outside the support of this kx tile is never transformed along z: do not produce it
-        if (support) { d.tile_range = support + n1 * (n0 / 16); d.tile_range_mode = 1; d.tile_range_k1 = 0; }
-        if (int rc = launch_2stage(ctx, p->axis[1], d, false, 0)) return rc;
-    }
-    {   // pass z: all columns (kx, ky), in place, stride n0 on both sides
-        ig_prof_scope prof(ctx, "fft_pad_z", (double)(n0 * n1 * b2 + vol) * C * 8.0);
-        PassDesc d{};
-        d.in = d.out = y; d.in_sj = d.out_sj = n0;
-        d.in_s[0] = d.out_s[0] = 1; d.in_s[1] = d.out_s[1] = n0 * n2; d.in_s[2] = d.out_s[2] = vol;
-        d.ext0 = n0; d.ext1 = n1; d.ncols = n0 * n1 * C;
-        d.in_lo = (int)l2; d.in_hi = (int)(l2 + b2); d.out_lo = 0; d.out_hi = (int)n2; d.inverse = 0;
-        d.tile_range = support; d.tile_range_mode = 1; d.tile_range_k1 = n0 / 16;   // only the support is ever gridded from
-        if (support) { d.tile_bits = reinterpret_cast<const uint32_t*>(support + n1 * (n0 / 16) + n0 / 16); d.tile_words = 16; }
-        if (int rc = launch_2stage(ctx, p->axis[2], d, false, 0)) return rc;
-    }
-    return IG_OK;
-}
-
-// phases: bit 0 = the z pass (whole grid), bit 1 = the y and x passes, restricted to the image planes z0 <= z' < z1
-static int exec_cropped_layout1(ig_fft* p, const float2* y, const float2* w, float2* x, int64_t x_bstride, float2* work,
-                                const short2* support, int phases = 3, int64_t z0 = 0, int64_t z1 = -1) {
-    ig_ctx* ctx = p->ctx;
-    const int64_t n0 = p->dims[0], n1 = p->dims[1], n2 = p->dims[2];
-    const int64_t b0 = p->box_dims[0], b1 = p->box_dims[1], b2 = p->box_dims[2];
-    const int64_t l0 = p->box_lo[0], l1 = p->box_lo[1], l2 = p->box_lo[2];
-    const int64_t vol = n0 * n1 * n2, bvol = b0 * b1 * b2, C = p->batch;
-    const int64_t cvol = n0 * b1 * b2;
-    float2* L1 = work + (size_t)p->total;
-    if (z1 < 0) z1 = b2;
-    const int64_t nz = z1 - z0;                      // image planes the y and x passes cover
-    if (phases & 1) {   // pass z: all columns (kx, ky), keep z in box, stride n0; input intact, result into the workspace
-        ig_prof_scope prof(ctx, "fft_crop_z", (double)(vol + n0 * n1 * b2) * C * 8.0);
-        PassDesc d{};
-        d.in = y; d.out = work; d.in_sj = d.out_sj = n0;
-        d.in_s[0] = d.out_s[0] = 1; d.in_s[1] = d.out_s[1] = n0 * n2; d.in_s[2] = d.out_s[2] = vol;
-        d.ext0 = n0; d.ext1 = n1; d.ncols = n0 * n1 * C;
-        d.in_lo = 0; d.in_hi = (int)n2; d.out_lo = (int)l2; d.out_hi = (int)(l2 + b2); d.inverse = 1;
-        d.tile_range = support; d.tile_range_mode = 2; d.tile_range_k1 = n0 / 16;   // the adjoint gridding only wrote the support
-        if (support) { d.tile_bits = reinterpret_cast<const uint32_t*>(support + n1 * (n0 / 16) + n0 / 16); d.tile_words = 16; }
-        if (support) d.k1_range = support + n1 * (n0 / 16);                         // ky the y pass will never read
-        if (int rc = launch_2stage(ctx, p->axis[2], d, false, 0)) return rc;
-    }
-    if (!(phases & 2) || nz <= 0) return IG_OK;
-    {   // pass y: columns (kx, z'), grid in (stride n0*n2), compact out, keep y in box
-        ig_prof_scope prof(ctx, "fft_crop_y", (double)(n0 * n1 * nz + n0 * b1 * nz) * C * 8.0);
-        PassDesc d{};
-        d.in = work + (l2 + z0) * n0; d.in_sj = n0 * n2; d.in_s[0] = 1; d.in_s[1] = n0; d.in_s[2] = vol;
-        d.out = L1 - l1 * n0 + z0 * n0 * b1; d.out_sj = n0; d.out_s[0] = 1; d.out_s[1] = n0 * b1; d.out_s[2] = cvol;
-        d.ext0 = n0; d.ext1 = nz; d.ncols = n0 * nz * C;
-        d.in_lo = 0; d.in_hi = (int)n1; d.out_lo = (int)l1; d.out_hi = (int)(l1 + b1); d.inverse = 1;
-        if (support) { d.tile_range = support + n1 * (n0 / 16); d.tile_range_mode = 2; d.tile_range_k1 = 0; }
-        if (int rc = launch_2stage(ctx, p->axis[1], d, false, 0)) return rc;
-    }
-    {   // pass x: compact rows, keep x in box, times conj(w), into the compact image array
-        ig_prof_scope prof(ctx, "fft_crop_x", (double)(cvol + bvol + (w ? bvol : 0)) * C * 8.0 * (double)nz / (double)b2);
-        PassDesc d{};
-        d.in = L1 + z0 * n0 * b1; d.in_sj = 1; d.in_s[0] = n0; d.in_s[1] = n0 * b1; d.in_s[2] = cvol;
-        d.out = x - l0 + z0 * b0 * b1; d.out_sj = 1; d.out_s[0] = b0; d.out_s[1] = b0 * b1; d.out_s[2] = x_bstride;
-        d.w = w ? w - l0 + z0 * b0 * b1 : nullptr; d.w_sj = 1; d.w_s[0] = b0; d.w_s[1] = b0 * b1; d.w_s[2] = bvol;
-        d.ext0 = b1; d.ext1 = nz; d.ncols = b1 * nz * C;
-        d.in_lo = 0; d.in_hi = (int)n0; d.out_lo = (int)l0; d.out_hi = (int)(l0 + b0); d.inverse = 1;
-        if (int rc = launch_2stage(ctx, p->axis[0], d, true, w ? 2 : 0)) return rc;
-    }
-    return IG_OK;
-}
-
-// Grid layout 2 interleaves the batch (coils) below layout 1: element (c, kx, ky, kz) lives at
+// Layout 2 interleaves the batch (coils) below layout 1: element (c, kx, ky, kz) lives at
 // c + C*(kx + n0*kz + n0*n2*ky).  The gridding matrix then reads / writes all C coils of a grid point as ONE
 // contiguous C*8-byte row instead of C separate 8-byte gathers a gigabyte apart (forward gridding of the 256^3 x 8
 // SENSE problem: 0.98 ms instead of 2.05 ms).  Every pass is a strided pass whose 16 lanes run over the combined
 // (c, kx) index -- for the x passes over (c, line) pairs, with the transform axis at stride C -- so all accesses stay
 // 128-byte (y, z) or 64*C/8-byte (x) contiguous.  The compact intermediate and, for the cropped transform, the
 // compact result are interleaved the same way; the weights must be too (w[(i)*C + c]).
+// (a one-row pitch on the z axis, to break the 16 MB power-of-two stride of the y pass, was measured: no gain once
+// the y pass runs on 32-column tiles)
+// How a pass carries the coil index follows from the layout as well (pass_strides): layouts 0 and 1 as the outermost extent;
+// layout 2 as a split of the tile's lanes on the x pass and folded into the row, (c, kx) at unit stride, on the y and z passes.
+typedef std::array<int64_t, 4> Strides;                // of (x, y, z, coil), in elements
+
+struct PaddedGeom {
+    int64_t n[3], b[3], l[3], C;                       // grid, box, the box's corner, coils
+    int64_t vol, bvol, cvol;                           // elements per coil of the grid, the image and the compact intermediate
+    bool interleaved;                                  // layout 2
+    Strides img, wgt, mid, grid;
+    bool mid_in_grid;                                  // layout 0: mid lives in the full-size array, mid_base elements in
+    int64_t mid_base;
+    // The k-space support table (layouts 1 and 2; snt = 0: the layout takes none).  Three parts: per (ky, kx tile) the kz hull
+    // of the samples [n1 * snt entries], per kx tile the ky hull [snt entries], then per (ky, kx tile) the kz bitmap of zw_in
+    // words in the order the z pass holds its INPUT and, where its output order differs (A x B axes), a second time with
+    // zw_out words in that order.
+    int64_t snt;                                       // entries per grid row: kx tiles of 16 (layout 2: support_tile) points
+    int tile_shift;                                    // log2 of the 16-column tiles of a row that share an entry
+    int zw_in, zw_out;
+    int64_t hull_y, bits, bits_out;                    // offsets of the ky hulls and the bitmaps (entries), of the output form (words)
+};
+
 static int lg2(int64_t v) { int s = 0; while ((1LL << s) < v) ++s; return s; }
 
-static int exec_padded_layout2(ig_fft* p, const float2* x, int64_t x_bstride, const float2* w, float2* y, float2* work,
-                               const short2* support) {
+// x_bstride: the image's coil stride where the layout does not fix it
+static PaddedGeom padded_geom(const ig_fft* p, bool inverse, int64_t x_bstride, bool sum_coils) {
+    PaddedGeom g{};
+    for (int a = 0; a < 3; ++a) { g.n[a] = p->dims[a]; g.b[a] = p->box_dims[a]; g.l[a] = p->box_lo[a]; }
+    const int64_t n0 = g.n[0], n1 = g.n[1], n2 = g.n[2], b0 = g.b[0], b1 = g.b[1], C = g.C = p->batch;
+    g.vol = n0 * n1 * n2; g.bvol = b0 * b1 * g.b[2]; g.cvol = n0 * b1 * g.b[2];
+    g.interleaved = p->layout == 2;
+    const int64_t k = g.interleaved ? C : 1;
+    // (the padded transform of layout 2 reads coil-planar images like the others: one image for all coils at x_bstride = 0)
+    if (g.interleaved && inverse) g.img = sum_coils ? Strides{1, b0, b0 * b1, 0} : Strides{C, C * b0, C * b0 * b1, 1};
+    else g.img = {1, b0, b0 * b1, x_bstride};
+    g.wgt = {k, k * b0, k * b0 * b1, g.interleaved ? 1 : g.bvol};
+    if (p->layout == 0) g.grid = {1, n0, n0 * n1, g.vol};
+    else g.grid = {k, k * n0 * n2, k * n0, g.interleaved ? 1 : g.vol};
+    g.mid_in_grid = p->layout == 0;
+    if (g.mid_in_grid) { g.mid = g.grid; g.mid_base = g.l[1] * n0 + g.l[2] * n0 * n1; }
+    else g.mid = {k, k * n0, k * n0 * b1, g.interleaved ? 1 : g.cvol};
+    if (p->layout >= 1) {
+        g.snt = n0 / p->support_tile;
+        g.tile_shift = g.interleaved ? lg2((int)(C * p->support_tile / 16)) : 0;
+        g.zw_in = p->zw_in; g.zw_out = p->zw_out;
+        g.hull_y = n1 * g.snt; g.bits = g.hull_y + g.snt;
+        g.bits_out = g.zw_out != g.zw_in ? n1 * g.snt * g.zw_in : 0;
+    }
+    return g;
+}
+
+// The arrays of one call: the image, the grid, the full-size array the y pass touches (padded: the grid itself, cropped: the
+// head of the workspace) and the intermediate.  (The side a transform reads is never written.)
+struct PaddedBufs { float2* img; float2* grid; float2* full; float2* mid; };
+
+static PaddedBufs padded_bufs(const ig_fft* p, const PaddedGeom& g, float2* img, float2* grid, float2* full, float2* work) {
+    return PaddedBufs{img, grid, full, g.mid_in_grid ? full + g.mid_base : work + (size_t)p->total};
+}
+
+// the strides of a pass along axis a through an array with strides S: transform axis, the two row axes, the coil
+static void pass_strides(const PaddedGeom& g, const Strides& S, int a, int64_t& sj, int64_t& sa, int64_t* s) {
+    sj = S[a]; s[0] = S[a == 0 ? 1 : 0]; s[1] = S[a == 2 ? 1 : 2];
+    if (!g.interleaved) s[2] = S[3];       // the outermost extent
+    else if (a == 0) sa = S[3];            // a lane split (PassDesc::cw)
+    else s[0] = S[3];                      // folded into the row
+}
+
+// A pass along axis a over rows of e0 x e1 columns.  One side of it holds the box only (padded: the input, cropped: the
+// output), the other side the full axis.
+static PassDesc pass_desc(const PaddedGeom& g, int a, bool inverse, float2* box, const Strides& box_s, float2* full, const Strides& full_s,
+                          int64_t e0, int64_t e1) {
+    PassDesc d{};
+    const bool lanes = g.interleaved && a == 0, folded = g.interleaved && a != 0;
+    const int lo = (int)g.l[a], hi = (int)(g.l[a] + g.b[a]), n = (int)g.n[a];
+    d.inverse = inverse ? 1 : 0;
+    d.in = inverse ? full : box; d.out = inverse ? box : full;
+    pass_strides(g, inverse ? full_s : box_s, a, d.in_sj, d.in_sa, d.in_s);
+    pass_strides(g, inverse ? box_s : full_s, a, d.out_sj, d.out_sa, d.out_s);
+    d.in_lo = inverse ? 0 : lo; d.in_hi = inverse ? n : hi; d.out_lo = inverse ? lo : 0; d.out_hi = inverse ? hi : n;
+    d.cw = lanes ? (int)g.C : 0;
+    d.ext0 = e0 * (folded ? g.C : 1); d.ext1 = e1; d.ncols = e0 * e1 * (lanes ? 1 : g.C);
+    return d;
+}
+
+// pass x over the image planes z0 <= z' < z0 + nz: lines (y', z') of the image box <-> rows of the intermediate; padded: times
+// w on the way in; cropped: times conj(w) into the image box, or (sum_coils) x = sum_c conj(w_c) .* crop(...), one image box
+static PassDesc pass_x(const PaddedGeom& g, bool inverse, const PaddedBufs& m, const float2* w, int64_t z0, int64_t nz, bool sum_coils,
+                       int& wmode, bool& axis0) {
+    PassDesc d = pass_desc(g, 0, inverse, m.img - g.l[0] * g.img[0] + z0 * g.img[2], g.img, m.mid + z0 * g.mid[2], g.mid, g.b[1], nz);
+    d.w = w ? w - g.l[0] * g.wgt[0] + z0 * g.wgt[2] : nullptr;
+    pass_strides(g, g.wgt, 0, d.w_sj, d.w_sa, d.w_s);
+    wmode = sum_coils ? 3 : !w ? 0 : inverse ? 2 : 1;
+    axis0 = !g.interleaved;                // contiguous columns, unless the coils sit below x
+    return d;
+}
+
+// pass y: columns (kx, z') for z0 <= z' < z0 + nz, y in the box on the intermediate's side, the planes z = l2 + z' of the
+// full-size array on the other
+static PassDesc pass_y(const PaddedGeom& g, bool inverse, const PaddedBufs& m, const short2* support, int64_t z0, int64_t nz) {
+    PassDesc d = pass_desc(g, 1, inverse, m.mid - g.l[1] * g.mid[1] + z0 * g.mid[2], g.mid, m.full + (g.l[2] + z0) * g.grid[2], g.grid, g.n[0], nz);
+    // padded: ky outside the support of this kx tile is never transformed along z: do not produce it; cropped: it reads as zero
+    if (support) { d.tile_range = support + g.hull_y; d.tile_range_mode = inverse ? 2 : 1; d.tile_range_k1 = 0; d.tile_shift = g.tile_shift; }
+    return d;
+}
+
+// pass z: all columns (kx, ky); padded: in place, inputs z in box; cropped: grid in, keep z in box, into the full-size array
+static PassDesc pass_z(const PaddedGeom& g, bool inverse, const PaddedBufs& m, const short2* support) {
+    PassDesc d = pass_desc(g, 2, inverse, m.full, g.grid, m.grid, g.grid, g.n[0], g.n[1]);
+    if (g.snt) {       // padded: only the support is ever gridded from; cropped: the adjoint gridding only wrote the support
+        d.tile_range = support; d.tile_range_mode = inverse ? 2 : 1; d.tile_range_k1 = g.snt; d.tile_shift = g.tile_shift;
+    }
+    // (round 5, measured on the padded pass: with the ky hulls for the early exit and range and bitmap read behind the loads, it took 1.029 ms against 1.010)
+    if (support) {     // the bitmaps in the order of the side they gate: the cropped pass's input, the padded pass's output
+        d.tile_bits = reinterpret_cast<const uint32_t*>(support + g.bits) + (inverse ? 0 : g.bits_out);
+        d.tile_words = inverse ? g.zw_in : g.zw_out;
+        if (inverse) d.k1_range = support + g.hull_y;          // ky the y pass will never read
+    }
+    return d;
+}
+
+static int exec_padded(ig_fft* p, float2* x, int64_t x_bstride, const float2* w, float2* y, float2* work, const short2* support) {
     ig_ctx* ctx = p->ctx;
-    const int64_t n0 = p->dims[0], n1 = p->dims[1], n2 = p->dims[2];
-    const int64_t snt = n0 / p->support_tile;                        // support entries per grid row
-    const int sshift = lg2((int)(p->batch * p->support_tile / 16));    // 16-column tiles per support entry
-    // (a one-row pitch on the z axis, to break the 16 MB power-of-two stride of the y pass, was measured: no gain once
-    // the y pass runs on 32-column tiles)
-    const int64_t b0 = p->box_dims[0], b1 = p->box_dims[1], b2 = p->box_dims[2];
-    const int64_t l0 = p->box_lo[0], l1 = p->box_lo[1], l2 = p->box_lo[2];
-    const int64_t vol = n0 * n1 * n2, bvol = b0 * b1 * b2, C = p->batch;
-    const int64_t cvol = n0 * b1 * b2;
-    float2* L1 = work + (size_t)p->total;
-    {   // pass x: lines (c, y', z') of the weighted image -> interleaved compact [c][kx][y'][z']
-        ig_prof_scope prof(ctx, "fft_pad_x", (double)(bvol + (w ? bvol : 0) + cvol) * C * 8.0);
-        PassDesc d{};
-        d.cw = (int)C;
-        d.in = x - l0; d.in_sj = 1; d.in_sa = x_bstride; d.in_s[0] = b0; d.in_s[1] = b0 * b1;
-        d.w = w ? w - l0 * C : nullptr; d.w_sj = C; d.w_sa = 1; d.w_s[0] = b0 * C; d.w_s[1] = b0 * b1 * C;
-        d.out = L1; d.out_sj = C; d.out_sa = 1; d.out_s[0] = C * n0; d.out_s[1] = C * n0 * b1;
-        d.ext0 = b1; d.ext1 = b2; d.ncols = b1 * b2;
-        d.in_lo = (int)l0; d.in_hi = (int)(l0 + b0); d.out_lo = 0; d.out_hi = (int)n0; d.inverse = 0;
-        if (int rc = launch_pass(ctx, p->axis[0], d, false, w ? 1 : 0)) return rc;
+    const PaddedGeom g = padded_geom(p, false, x_bstride, false);
+    const PaddedBufs m = padded_bufs(p, g, x, y, y, work);
+    const int64_t plane = g.n[0] * g.n[1], b2 = g.b[2];
+    {
+        ig_prof_scope prof(ctx, "fft_pad_x", (double)(g.bvol + (w ? g.bvol : 0) + g.cvol) * g.C * 8.0);
+        int wmode; bool axis0;
+        const PassDesc d = pass_x(g, false, m, w, 0, b2, false, wmode, axis0);
+        if (int rc = launch_pass(ctx, p->axis[0], d, axis0, wmode)) return rc;
     }
-    {   // pass y: columns (c + C*kx, z')
-        ig_prof_scope prof(ctx, "fft_pad_y", (double)(cvol + n0 * n1 * b2) * C * 8.0);
-        PassDesc d{};
-        d.in = L1 - l1 * C * n0; d.in_sj = C * n0; d.in_s[0] = 1; d.in_s[1] = C * n0 * b1;
-        d.out = y + l2 * C * n0; d.out_sj = C * n0 * n2; d.out_s[0] = 1; d.out_s[1] = C * n0;
-        d.ext0 = C * n0; d.ext1 = b2; d.ncols = C * n0 * b2;
-        d.in_lo = (int)l1; d.in_hi = (int)(l1 + b1); d.out_lo = 0; d.out_hi = (int)n1; d.inverse = 0;
-        if (support) { d.tile_range = support + n1 * snt; d.tile_range_mode = 1; d.tile_range_k1 = 0; d.tile_shift = sshift; }
-        if (int rc = launch_pass(ctx, p->axis[1], d, false, 0)) return rc;
+    {
+        ig_prof_scope prof(ctx, "fft_pad_y", (double)(g.cvol + plane * b2) * g.C * 8.0);
+        if (int rc = launch_pass(ctx, p->axis[1], pass_y(g, false, m, support, 0, b2), false, 0)) return rc;
     }
-    {   // pass z: columns (c + C*kx, ky), in place
-        ig_prof_scope prof(ctx, "fft_pad_z", (double)(n0 * n1 * b2 + vol) * C * 8.0);
-        PassDesc d{};
-        d.in = d.out = y; d.in_sj = d.out_sj = C * n0;
-        d.in_s[0] = d.out_s[0] = 1; d.in_s[1] = d.out_s[1] = C * n0 * n2;
-        d.ext0 = C * n0; d.ext1 = n1; d.ncols = C * n0 * n1;
-        d.in_lo = (int)l2; d.in_hi = (int)(l2 + b2); d.out_lo = 0; d.out_hi = (int)n2; d.inverse = 0;
-        d.tile_range = support; d.tile_range_mode = 1; d.tile_range_k1 = snt; d.tile_shift = sshift;
-        // (round 5, measured: with the ky hulls for the early exit and range and bitmap read behind the loads, this pass took 1.029 ms against 1.010)
-        if (support) {      // the output-side form of the bitmaps (it follows the input-side form where the two differ)
-            d.tile_bits = reinterpret_cast<const uint32_t*>(support + n1 * snt + snt) + (p->zw_out != p->zw_in ? n1 * snt * p->zw_in : 0);
-            d.tile_words = p->zw_out;
-        }
-        if (int rc = launch_pass(ctx, p->axis[2], d, false, 0)) return rc;
+    {
+        ig_prof_scope prof(ctx, "fft_pad_z", (double)(plane * b2 + g.vol) * g.C * 8.0);
+        if (int rc = launch_pass(ctx, p->axis[2], pass_z(g, false, m, support), false, 0)) return rc;
     }
     return IG_OK;
 }
 
 // phases: bit 0 = the z pass (whole grid), bit 1 = the y and x passes, restricted to the image planes z0 <= z' < z1
-static int exec_cropped_layout2(ig_fft* p, const float2* y, const float2* w, float2* x, float2* work, const short2* support,
-                                bool sum_coils = false, int phases = 3, int64_t z0 = 0, int64_t z1 = -1) {
+static int exec_cropped(ig_fft* p, float2* y, const float2* w, float2* x, int64_t x_bstride, float2* work, const short2* support,
+                        bool sum_coils, int phases, int64_t z0, int64_t z1) {
     ig_ctx* ctx = p->ctx;
-    const int64_t n0 = p->dims[0], n1 = p->dims[1], n2 = p->dims[2];
-    const int64_t snt = n0 / p->support_tile;                        // support entries per grid row
-    const int sshift = lg2((int)(p->batch * p->support_tile / 16));    // 16-column tiles per support entry
-    const int64_t b0 = p->box_dims[0], b1 = p->box_dims[1], b2 = p->box_dims[2];
-    const int64_t l0 = p->box_lo[0], l1 = p->box_lo[1], l2 = p->box_lo[2];
-    const int64_t vol = n0 * n1 * n2, bvol = b0 * b1 * b2, C = p->batch;
-    const int64_t cvol = n0 * b1 * b2;
-    float2* L1 = work + (size_t)p->total;
-    if (z1 < 0) z1 = b2;
+    const PaddedGeom g = padded_geom(p, true, x_bstride, sum_coils);
+    const PaddedBufs m = padded_bufs(p, g, x, y, work, work);
+    const int64_t plane = g.n[0] * g.n[1], b2 = g.b[2];
     const int64_t nz = z1 - z0;                      // image planes the y and x passes cover
-    if (phases & 1) {   // pass z: input intact, result into the workspace
-        ig_prof_scope prof(ctx, "fft_crop_z", (double)(vol + n0 * n1 * b2) * C * 8.0);
-        PassDesc d{};
-        d.in = y; d.out = work; d.in_sj = d.out_sj = C * n0;
-        d.in_s[0] = d.out_s[0] = 1; d.in_s[1] = d.out_s[1] = C * n0 * n2;
-        d.ext0 = C * n0; d.ext1 = n1; d.ncols = C * n0 * n1;
-        d.in_lo = 0; d.in_hi = (int)n2; d.out_lo = (int)l2; d.out_hi = (int)(l2 + b2); d.inverse = 1;
-        d.tile_range = support; d.tile_range_mode = 2; d.tile_range_k1 = snt; d.tile_shift = sshift;
-        if (support) { d.tile_bits = reinterpret_cast<const uint32_t*>(support + n1 * snt + snt); d.tile_words = p->zw_in; }
-        if (support) d.k1_range = support + n1 * snt;                         // ky the y pass will never read
-        if (int rc = launch_pass(ctx, p->axis[2], d, false, 0)) return rc;
+    if (phases & 1) {
+        ig_prof_scope prof(ctx, "fft_crop_z", (double)(g.vol + plane * b2) * g.C * 8.0);
+        if (int rc = launch_pass(ctx, p->axis[2], pass_z(g, true, m, support), false, 0)) return rc;
     }
     if (!(phases & 2) || nz <= 0) return IG_OK;
-    {   // pass y
-        ig_prof_scope prof(ctx, "fft_crop_y", (double)(n0 * n1 * nz + n0 * b1 * nz) * C * 8.0);
-        PassDesc d{};
-        d.in = work + (l2 + z0) * C * n0; d.in_sj = C * n0 * n2; d.in_s[0] = 1; d.in_s[1] = C * n0;
-        d.out = L1 - l1 * C * n0 + z0 * C * n0 * b1; d.out_sj = C * n0; d.out_s[0] = 1; d.out_s[1] = C * n0 * b1;
-        d.ext0 = C * n0; d.ext1 = nz; d.ncols = C * n0 * nz;
-        d.in_lo = 0; d.in_hi = (int)n1; d.out_lo = (int)l1; d.out_hi = (int)(l1 + b1); d.inverse = 1;
-        if (support) { d.tile_range = support + n1 * snt; d.tile_range_mode = 2; d.tile_range_k1 = 0; d.tile_shift = sshift; }
-        if (int rc = launch_pass(ctx, p->axis[1], d, false, 0)) return rc;
+    {
+        ig_prof_scope prof(ctx, "fft_crop_y", (double)(plane * nz + g.n[0] * g.b[1] * nz) * g.C * 8.0);
+        if (int rc = launch_pass(ctx, p->axis[1], pass_y(g, true, m, support, z0, nz), false, 0)) return rc;
     }
-    if (sum_coils) {   // pass x with the coil combination: x = sum_c conj(w_c) .* crop(...), one image box
-        ig_prof_scope prof(ctx, "fft_crop_x", ((double)(cvol + bvol) * C * 8.0 + (double)bvol * 8.0) * (double)nz / (double)b2);
-        PassDesc d{};
-        d.cw = (int)C;
-        d.in = L1 + z0 * C * n0 * b1; d.in_sj = C; d.in_sa = 1; d.in_s[0] = C * n0; d.in_s[1] = C * n0 * b1;
-        d.out = x - l0 + z0 * b0 * b1; d.out_sj = 1; d.out_sa = 0; d.out_s[0] = b0; d.out_s[1] = b0 * b1;
-        d.w = w - l0 * C + z0 * b0 * b1 * C; d.w_sj = C; d.w_sa = 1; d.w_s[0] = b0 * C; d.w_s[1] = b0 * b1 * C;
-        d.ext0 = b1; d.ext1 = nz; d.ncols = b1 * nz;
-        d.in_lo = 0; d.in_hi = (int)n0; d.out_lo = (int)l0; d.out_hi = (int)(l0 + b0); d.inverse = 1;
-        if (int rc = launch_pass(ctx, p->axis[0], d, false, 3)) return rc;
-    } else
-    {   // pass x: interleaved compact rows -> interleaved compact image box, times conj(w)
-        ig_prof_scope prof(ctx, "fft_crop_x", (double)(cvol + bvol + (w ? bvol : 0)) * C * 8.0);
-        PassDesc d{};
-        d.cw = (int)C;
-        d.in = L1; d.in_sj = C; d.in_sa = 1; d.in_s[0] = C * n0; d.in_s[1] = C * n0 * b1;
-        d.out = x - l0 * C; d.out_sj = C; d.out_sa = 1; d.out_s[0] = b0 * C; d.out_s[1] = b0 * b1 * C;
-        d.w = w ? w - l0 * C : nullptr; d.w_sj = C; d.w_sa = 1; d.w_s[0] = b0 * C; d.w_s[1] = b0 * b1 * C;
-        d.ext0 = b1; d.ext1 = b2; d.ncols = b1 * b2;
-        d.in_lo = 0; d.in_hi = (int)n0; d.out_lo = (int)l0; d.out_hi = (int)(l0 + b0); d.inverse = 1;
-        if (int rc = launch_pass(ctx, p->axis[0], d, false, w ? 2 : 0)) return rc;
+    {
+        const double bytes = sum_coils ? (double)(g.cvol + g.bvol) * g.C * 8.0 + (double)g.bvol * 8.0 : (double)(g.cvol + g.bvol + (w ? g.bvol : 0)) * g.C * 8.0;
+        ig_prof_scope prof(ctx, "fft_crop_x", bytes * (double)nz / (double)b2);
+        int wmode; bool axis0;
+        const PassDesc d = pass_x(g, true, m, w, z0, nz, sum_coils, wmode, axis0);
+        if (int rc = launch_pass(ctx, p->axis[0], d, axis0, wmode)) return rc;
     }
     return IG_OK;
 }
@@ -2105,150 +2066,58 @@ int ig_fft_set_support_tile(ig_fft* p, int tile) {
     return IG_OK;
 }
 
+// The checks the five exec entry points share.  fn: the entry point's name; need_layout: the grid layout it is for, or -1;
+// arrays: whether every array it needs was given; slab: whether phase, z0 and z1 are arguments of the call.
+static int check_padded_exec(ig_fft* p, const char* fn, int need_layout, bool arrays, const int16_t* support,
+                             bool slab = false, int phase = 0, int64_t z0 = 0, int64_t z1 = 0) {
+    if (!p) return ig_fail(nullptr, IG_ERR_ARG, "%s: plan is NULL", fn);
+    ig_ctx* ctx = p->ctx;
+    if (need_layout == 1) IG_REQUIRE(ctx, p->padded && p->layout == 1, "%s: needs a plan of ig_fft_plan_padded with grid_layout 1 (layout 2: ig_fft_exec_cropped_sum_slab)", fn);
+    else if (need_layout == 2) IG_REQUIRE(ctx, p->padded && p->layout == 2, "%s: needs a plan of ig_fft_plan_padded with grid_layout 2", fn);
+    else IG_REQUIRE(ctx, p->padded, "%s: plan was not made by ig_fft_plan_padded", fn);
+    IG_REQUIRE(ctx, arrays, "%s: NULL array", fn);
+    // (a grid with a chirp-z axis takes the table's hulls; its bitmaps are not read)
+    IG_REQUIRE(ctx, !support || (p->layout >= 1 && (!p->has_chirp_axis || p->layout == 2)), "%s: a support table needs grid layout 1 or 2 (chirp-z axes: layout 2, hulls only)", fn);
+    if (slab) {
+        IG_REQUIRE(ctx, phase == 0 || phase == 1, "%s: phase must be 0 (z pass) or 1 (y and x passes of a slab)", fn);
+        IG_REQUIRE(ctx, phase == 0 || (0 <= z0 && z0 <= z1 && z1 <= p->box_dims[2]),
+                   "%s: slab [%lld, %lld) outside the image's %lld planes", fn, (long long)z0, (long long)z1, (long long)p->box_dims[2]);
+    }
+    return ig_set_device(ctx);
+}
+
 int ig_fft_exec_padded(ig_fft* p, const void* xv, int64_t x_bstride, const void* wv, void* yv, void* workspace,
                        const int16_t* support) {
-    if (!p) return ig_fail(nullptr, IG_ERR_ARG, "ig_fft_exec_padded: plan is NULL");
-    ig_ctx* ctx = p->ctx;
-    IG_REQUIRE(ctx, p->padded, "ig_fft_exec_padded: plan was not made by ig_fft_plan_padded");
-    IG_REQUIRE(ctx, xv && yv, "ig_fft_exec_padded: NULL array");
-    IG_REQUIRE(ctx, p->layout == 0 || workspace, "ig_fft_exec_padded: grid layouts 1 and 2 need the workspace");
-    if (int rc = ig_set_device(ctx)) return rc;
-    IG_REQUIRE(ctx, !support || (p->layout >= 1 && (!p->has_chirp_axis || p->layout == 2)), "ig_fft_exec_padded: a support table needs grid layout 1 or 2 (chirp-z axes: layout 2, hulls only)");
-    if (p->layout == 2)
-        return exec_padded_layout2(p, (const float2*)xv, x_bstride, (const float2*)wv, (float2*)yv, (float2*)workspace,
-                                   (const short2*)support);
-    if (p->layout == 1)
-        return exec_padded_layout1(p, (const float2*)xv, x_bstride, (const float2*)wv, (float2*)yv, (float2*)workspace,
-                                   (const short2*)support);
-    const int64_t n0 = p->dims[0], n1 = p->dims[1], n2 = p->dims[2];
-    const int64_t b0 = p->box_dims[0], b1 = p->box_dims[1], b2 = p->box_dims[2];
-    const int64_t l0 = p->box_lo[0], l1 = p->box_lo[1], l2 = p->box_lo[2];
-    const int64_t vol = n0 * n1 * n2, bvol = b0 * b1 * b2, C = p->batch;
-    const float2* x = (const float2*)xv;
-    const float2* w = (const float2*)wv;
-    float2* y = (float2*)yv;
-    {   // pass x: compact (weighted) image rows -> full-length rows at the box's (y, z) positions
-        ig_prof_scope prof(ctx, "fft_pad_x", (double)(bvol + (w ? bvol : 0) + n0 * b1 * b2) * C * 8.0);
-        PassDesc d{};
-        d.in = x - l0; d.in_sj = 1; d.in_s[0] = b0; d.in_s[1] = b0 * b1; d.in_s[2] = x_bstride;
-        d.w = w ? w - l0 : nullptr; d.w_sj = 1; d.w_s[0] = b0; d.w_s[1] = b0 * b1; d.w_s[2] = bvol;
-        d.out = y + l1 * n0 + l2 * n0 * n1; d.out_sj = 1; d.out_s[0] = n0; d.out_s[1] = n0 * n1; d.out_s[2] = vol;
-        d.ext0 = b1; d.ext1 = b2; d.ncols = b1 * b2 * C;
-        d.in_lo = (int)l0; d.in_hi = (int)(l0 + b0); d.out_lo = 0; d.out_hi = (int)n0; d.inverse = 0;
-        if (int rc = launch_2stage(ctx, p->axis[0], d, true, w ? 1 : 0)) return rc;
-    }
-    {   // pass y: columns (kx, z in box), inputs y in box
-        ig_prof_scope prof(ctx, "fft_pad_y", (double)(n0 * b1 * b2 + n0 * n1 * b2) * C * 8.0);
-        PassDesc d{};
-        d.in = d.out = y + l2 * n0 * n1; d.in_sj = d.out_sj = n0;
-        d.in_s[0] = d.out_s[0] = 1; d.in_s[1] = d.out_s[1] = n0 * n1; d.in_s[2] = d.out_s[2] = vol;
-        d.ext0 = n0; d.ext1 = b2; d.ncols = n0 * b2 * C;
-        d.in_lo = (int)l1; d.in_hi = (int)(l1 + b1); d.out_lo = 0; d.out_hi = (int)n1; d.inverse = 0;
-        if (int rc = launch_2stage(ctx, p->axis[1], d, false, 0)) return rc;
-    }
-    {   // pass z: all columns (kx, ky), inputs z in box
-        ig_prof_scope prof(ctx, "fft_pad_z", (double)(n0 * n1 * b2 + vol) * C * 8.0);
-        PassDesc d{};
-        d.in = d.out = y; d.in_sj = d.out_sj = n0 * n1;
-        d.in_s[0] = d.out_s[0] = 1; d.in_s[1] = d.out_s[1] = n0; d.in_s[2] = d.out_s[2] = vol;
-        d.ext0 = n0; d.ext1 = n1; d.ncols = n0 * n1 * C;
-        d.in_lo = (int)l2; d.in_hi = (int)(l2 + b2); d.out_lo = 0; d.out_hi = (int)n2; d.inverse = 0;
-        if (int rc = launch_2stage(ctx, p->axis[2], d, false, 0)) return rc;
-    }
-    return IG_OK;
+    if (int rc = check_padded_exec(p, "ig_fft_exec_padded", -1, xv && yv, support)) return rc;
+    IG_REQUIRE(p->ctx, p->layout == 0 || workspace, "ig_fft_exec_padded: grid layouts 1 and 2 need the workspace");
+    return exec_padded(p, (float2*)xv, x_bstride, (const float2*)wv, (float2*)yv, (float2*)workspace, (const short2*)support);
 }
 
 int ig_fft_exec_cropped(ig_fft* p, const void* yv, const void* wv, void* xv, int64_t x_bstride, void* workspace,
                         const int16_t* support) {
-    if (!p) return ig_fail(nullptr, IG_ERR_ARG, "ig_fft_exec_cropped: plan is NULL");
-    ig_ctx* ctx = p->ctx;
-    IG_REQUIRE(ctx, p->padded, "ig_fft_exec_cropped: plan was not made by ig_fft_plan_padded");
-    IG_REQUIRE(ctx, xv && yv && workspace, "ig_fft_exec_cropped: NULL array");
-    if (int rc = ig_set_device(ctx)) return rc;
-    IG_REQUIRE(ctx, !support || (p->layout >= 1 && (!p->has_chirp_axis || p->layout == 2)), "ig_fft_exec_cropped: a support table needs grid layout 1 or 2 (chirp-z axes: layout 2, hulls only)");
-    if (p->layout == 2)
-        return exec_cropped_layout2(p, (const float2*)yv, (const float2*)wv, (float2*)xv, (float2*)workspace,
-                                    (const short2*)support);
-    if (p->layout == 1)
-        return exec_cropped_layout1(p, (const float2*)yv, (const float2*)wv, (float2*)xv, x_bstride, (float2*)workspace,
-                                    (const short2*)support);
-    const int64_t n0 = p->dims[0], n1 = p->dims[1], n2 = p->dims[2];
-    const int64_t b0 = p->box_dims[0], b1 = p->box_dims[1], b2 = p->box_dims[2];
-    const int64_t l0 = p->box_lo[0], l1 = p->box_lo[1], l2 = p->box_lo[2];
-    const int64_t vol = n0 * n1 * n2, bvol = b0 * b1 * b2, C = p->batch;
-    const float2* y = (const float2*)yv;
-    const float2* w = (const float2*)wv;
-    float2* x = (float2*)xv;
-    float2* work = (float2*)workspace;
-    {   // pass z: all columns, keep z in box (input stays intact: written to the workspace)
-        ig_prof_scope prof(ctx, "fft_crop_z", (double)(vol + n0 * n1 * b2) * C * 8.0);
-        PassDesc d{};
-        d.in = y; d.out = work; d.in_sj = d.out_sj = n0 * n1;
-        d.in_s[0] = d.out_s[0] = 1; d.in_s[1] = d.out_s[1] = n0; d.in_s[2] = d.out_s[2] = vol;
-        d.ext0 = n0; d.ext1 = n1; d.ncols = n0 * n1 * C;
-        d.in_lo = 0; d.in_hi = (int)n2; d.out_lo = (int)l2; d.out_hi = (int)(l2 + b2); d.inverse = 1;
-        if (int rc = launch_2stage(ctx, p->axis[2], d, false, 0)) return rc;
-    }
-    {   // pass y: columns (kx, z in box), keep y in box
-        ig_prof_scope prof(ctx, "fft_crop_y", (double)(n0 * n1 * b2 + n0 * b1 * b2) * C * 8.0);
-        PassDesc d{};
-        d.in = d.out = work + l2 * n0 * n1; d.in_sj = d.out_sj = n0;
-        d.in_s[0] = d.out_s[0] = 1; d.in_s[1] = d.out_s[1] = n0 * n1; d.in_s[2] = d.out_s[2] = vol;
-        d.ext0 = n0; d.ext1 = b2; d.ncols = n0 * b2 * C;
-        d.in_lo = 0; d.in_hi = (int)n1; d.out_lo = (int)l1; d.out_hi = (int)(l1 + b1); d.inverse = 1;
-        if (int rc = launch_2stage(ctx, p->axis[1], d, false, 0)) return rc;
-    }
-    {   // pass x: rows (y, z in box), keep x in box, times conj(w), into the compact array
-        ig_prof_scope prof(ctx, "fft_crop_x", (double)(n0 * b1 * b2 + bvol + (w ? bvol : 0)) * C * 8.0);
-        PassDesc d{};
-        d.in = work + l1 * n0 + l2 * n0 * n1; d.in_sj = 1; d.in_s[0] = n0; d.in_s[1] = n0 * n1; d.in_s[2] = vol;
-        d.out = x - l0; d.out_sj = 1; d.out_s[0] = b0; d.out_s[1] = b0 * b1; d.out_s[2] = x_bstride;
-        d.w = w ? w - l0 : nullptr; d.w_sj = 1; d.w_s[0] = b0; d.w_s[1] = b0 * b1; d.w_s[2] = bvol;
-        d.ext0 = b1; d.ext1 = b2; d.ncols = b1 * b2 * C;
-        d.in_lo = 0; d.in_hi = (int)n0; d.out_lo = (int)l0; d.out_hi = (int)(l0 + b0); d.inverse = 1;
-        if (int rc = launch_2stage(ctx, p->axis[0], d, true, w ? 2 : 0)) return rc;
-    }
-    return IG_OK;
+    if (int rc = check_padded_exec(p, "ig_fft_exec_cropped", -1, xv && yv && workspace, support)) return rc;
+    return exec_cropped(p, (float2*)yv, (const float2*)wv, (float2*)xv, x_bstride, (float2*)workspace, (const short2*)support,
+                        false, 3, 0, p->box_dims[2]);
 }
 
 int ig_fft_exec_cropped_slab(ig_fft* p, const void* yv, const void* wv, void* xv, int64_t x_bstride, void* workspace,
                              const int16_t* support, int phase, int64_t z0, int64_t z1) {
-    if (!p) return ig_fail(nullptr, IG_ERR_ARG, "ig_fft_exec_cropped_slab: plan is NULL");
-    ig_ctx* ctx = p->ctx;
-    IG_REQUIRE(ctx, p->padded && p->layout == 1, "ig_fft_exec_cropped_slab: needs a plan of ig_fft_plan_padded with grid_layout 1 (layout 2: ig_fft_exec_cropped_sum_slab)");
-    IG_REQUIRE(ctx, xv && yv && workspace, "ig_fft_exec_cropped_slab: NULL array");
-    IG_REQUIRE(ctx, phase == 0 || phase == 1, "ig_fft_exec_cropped_slab: phase must be 0 (z pass) or 1 (y and x passes of a slab)");
-    IG_REQUIRE(ctx, phase == 0 || (0 <= z0 && z0 <= z1 && z1 <= p->box_dims[2]),
-               "ig_fft_exec_cropped_slab: slab [%lld, %lld) outside the image's %lld planes", (long long)z0, (long long)z1, (long long)p->box_dims[2]);
-    if (int rc = ig_set_device(ctx)) return rc;
-    return exec_cropped_layout1(p, (const float2*)yv, (const float2*)wv, (float2*)xv, x_bstride, (float2*)workspace,
-                                (const short2*)support, phase == 0 ? 1 : 2, z0, z1);
+    if (int rc = check_padded_exec(p, "ig_fft_exec_cropped_slab", 1, xv && yv && workspace, support, true, phase, z0, z1)) return rc;
+    return exec_cropped(p, (float2*)yv, (const float2*)wv, (float2*)xv, x_bstride, (float2*)workspace, (const short2*)support,
+                        false, phase == 0 ? 1 : 2, z0, z1);
 }
 
 int ig_fft_exec_cropped_sum(ig_fft* p, const void* yv, const void* wv, void* xv, void* workspace, const int16_t* support) {
-    if (!p) return ig_fail(nullptr, IG_ERR_ARG, "ig_fft_exec_cropped_sum: plan is NULL");
-    ig_ctx* ctx = p->ctx;
-    IG_REQUIRE(ctx, p->padded && p->layout == 2, "ig_fft_exec_cropped_sum: needs a plan of ig_fft_plan_padded with grid_layout 2");
-    IG_REQUIRE(ctx, xv && yv && wv && workspace, "ig_fft_exec_cropped_sum: NULL array");
-    // (a grid with a chirp-z axis takes the table's hulls; its bitmaps are not read)
-    if (int rc = ig_set_device(ctx)) return rc;
-    return exec_cropped_layout2(p, (const float2*)yv, (const float2*)wv, (float2*)xv, (float2*)workspace,
-                                (const short2*)support, true);
+    if (int rc = check_padded_exec(p, "ig_fft_exec_cropped_sum", 2, xv && yv && wv && workspace, support)) return rc;
+    return exec_cropped(p, (float2*)yv, (const float2*)wv, (float2*)xv, 0, (float2*)workspace, (const short2*)support,
+                        true, 3, 0, p->box_dims[2]);
 }
 
 int ig_fft_exec_cropped_sum_slab(ig_fft* p, const void* yv, const void* wv, void* xv, void* workspace, const int16_t* support,
                                  int phase, int64_t z0, int64_t z1) {
-    if (!p) return ig_fail(nullptr, IG_ERR_ARG, "ig_fft_exec_cropped_sum_slab: plan is NULL");
-    ig_ctx* ctx = p->ctx;
-    IG_REQUIRE(ctx, p->padded && p->layout == 2, "ig_fft_exec_cropped_sum_slab: needs a plan of ig_fft_plan_padded with grid_layout 2");
-    IG_REQUIRE(ctx, xv && yv && wv && workspace, "ig_fft_exec_cropped_sum_slab: NULL array");
-    IG_REQUIRE(ctx, phase == 0 || phase == 1, "ig_fft_exec_cropped_sum_slab: phase must be 0 (z pass) or 1 (y and x passes of a slab)");
-    IG_REQUIRE(ctx, phase == 0 || (0 <= z0 && z0 <= z1 && z1 <= p->box_dims[2]),
-               "ig_fft_exec_cropped_sum_slab: slab [%lld, %lld) outside the image's %lld planes", (long long)z0, (long long)z1, (long long)p->box_dims[2]);
-
-    if (int rc = ig_set_device(ctx)) return rc;
-    return exec_cropped_layout2(p, (const float2*)yv, (const float2*)wv, (float2*)xv, (float2*)workspace,
-                                (const short2*)support, true, phase == 0 ? 1 : 2, z0, z1);
+    if (int rc = check_padded_exec(p, "ig_fft_exec_cropped_sum_slab", 2, xv && yv && wv && workspace, support, true, phase, z0, z1)) return rc;
+    return exec_cropped(p, (float2*)yv, (const float2*)wv, (float2*)xv, 0, (float2*)workspace, (const short2*)support,
+                        true, phase == 0 ? 1 : 2, z0, z1);
 }
 
 int ig_fft_inplace_workspace(ig_fft* p, size_t* bytes) {

@@ -322,6 +322,43 @@ def test_padded_and_cropped_fft_leaves(hip, grid, box, lo, C, weighted, layout):
                                np.vdot(s_d.to_host().astype(c128), x.astype(c128)), rtol=1e-4)
 
 
+@pytest.mark.parametrize("grid,box,lo,C,summed", [
+    ((256, 256, 256), (100, 77, 130), (5, 100, 126), 1, False),      # layout 1 through ifft_cropped
+    ((128, 144, 160), (64, 72, 80), None, 4, True),                   # layout 2 with the coil sum through ifft_cropped_sum
+])
+def test_cropped_fft_slabs_equal_the_whole(hip, grid, box, lo, C, summed):
+    """the slab arguments of the cropped transforms at the leaf: slab='z' followed by the slabs with edges [0, 1, b2 // 3, b2]
+    gives, bit for bit, what one call over everything gives"""
+    hip._scratch = None
+    lo = lo or tuple(m // 2 + int(np.ceil(-n / 2)) for m, n in zip(grid, box))
+    P, N = int(np.prod(grid)), int(np.prod(box))
+    w = rand64c(N, C, seed=2)
+    k = rand64c(P, C, seed=3)
+    if summed:
+        w_d, k_d = hip.copy_array(np.ascontiguousarray(w).reshape(-1)), hip.copy_array(k.reshape(-1)).reshape((P, C))
+        ws = hip.zero_array((hip._fft_padded_workspace(grid, lo, box, C, 2) // 8,), C64)
+
+        def run(out_d, slab):
+            hip.ifft_cropped_sum(out_d, k_d, w_d, grid, lo, box, ws, slab=slab)
+    else:
+        w_d, k_d = hip.copy_array(w), hip.copy_array(k)
+        ws = hip.zero_array((hip._fft_padded_workspace(grid, lo, box, C, 1) // 8,), C64)
+
+        def run(out_d, slab):
+            hip.ifft_cropped(out_d, k_d, w_d, grid, lo, box, ws, 1, slab=slab)
+    nan = np.full((N, 1 if summed else C), np.nan, dtype=C64, order='F')
+    whole_d, slabs_d = hip.copy_array(nan), hip.copy_array(nan)
+    run(whole_d, None)
+    whole = whole_d.to_host()
+    assert np.isfinite(whole.view(np.float32)).all()
+    run(slabs_d, 'z')
+    edges = [0, 1, box[2] // 3, box[2]]
+    for z0, z1 in zip(edges[:-1], edges[1:]):
+        run(slabs_d, (z0, z1))
+    np.testing.assert_array_equal(slabs_d.to_host(), whole)
+    hip._scratch = None
+
+
 def test_sum_columns(hip):
     X = rand64c(1000, 7, seed=1)
     y = rand64c(1000, 1, seed=2)
