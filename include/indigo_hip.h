@@ -195,6 +195,21 @@ int  ig_dwt3_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int wavelet, i
  * ncols F-ordered n0 x n1 x n2 columns; |x| <= tau gives exactly 0, the coarse box is not touched.                          */
 int  ig_csoft_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t c0, int64_t c1, int64_t c2, int64_t ncols,
                   float tau, void* x, int64_t ldx);
+/* Forward-difference gradient, its adjoint and the fused dual step of isotropic total variation (operators.Gradient,
+ * Backend.grad3 / tv_dual_step, pics --tv).  No reference counterpart.  A column of x is an F-ordered
+ * n0 x n1 x n2 volume of N voxels, a column of u its three difference components, component a in rows [aN, (a+1)N):
+ *   (D_a x)[i] = x[i + e_a] - x[i] if i_a < n_a - 1, else 0;   (D^H u)[i] = sum_a ((i_a > 0 ? u_a[i - e_a] : 0) - (i_a < n_a - 1 ? u_a[i] : 0)).
+ * ig_grad3_c64:   y[:, j] = beta*y[:, j] + alpha * D x[:, j]     (y: 3N x ncols, ldy >= 3N; x: N x ncols, ldx >= N)
+ * ig_grad3h_c64:  y[:, j] = beta*y[:, j] + alpha * D^H u[:, j]   (y: N x ncols; u: 3N x ncols)
+ * beta == 0: y is not read.  These are stencils: an output panel that overlaps an input panel is IG_ERR_ARG.               */
+int  ig_grad3_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t ncols, const void* x, int64_t ldx,
+                  float alpha_re, float alpha_im, float beta_re, float beta_im, void* y, int64_t ldy);
+int  ig_grad3h_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t ncols, const void* u, int64_t ldu,
+                   float alpha_re, float alpha_im, float beta_re, float beta_im, void* y, int64_t ldy);
+/* u[:, j] <- proj_mu(u[:, j] + sigma * D(2*xn[:, j] - xo[:, j])) in place: per voxel, with r = sqrt(sum_a |u_a[i]|^2), the
+ * three components are scaled by (r <= mu ? 1 : mu / r).  mu >= 0; u must overlap neither xn nor xo (xn may be xo).         */
+int  ig_tv_dual_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t ncols, const void* xn, int64_t ldxn,
+                    const void* xo, int64_t ldxo, float sigma, float mu, void* u, int64_t ldu);
 
 /* ------------------------------------------------------------------------
  * CSR x dense-panel SpMM.  Replaces Backend.ccsrmm

@@ -67,6 +67,28 @@ def dwt_plan(dims, wavelet, levels):
     return passes, tuple(c)
 
 
+def _grad_forward(v):
+    """D v for v of shape dims + (ncols,): shape dims + (3, ncols) -- the F-ordered 3N-row columns of Backend.grad3 -- forward
+    differences, zero at the far face"""
+    out = np.zeros(v.shape[:3] + (3,) + v.shape[3:], dtype=v.dtype)
+    out[:-1, :, :, 0] = v[1:] - v[:-1]
+    out[:, :-1, :, 1] = v[:, 1:] - v[:, :-1]
+    out[:, :, :-1, 2] = v[:, :, 1:] - v[:, :, :-1]
+    return out
+
+
+def _grad_adjoint(t):
+    """D^H t for t of shape dims + (3, ncols): shape dims + (ncols,); t on the far face of its own axis is not read"""
+    out = np.zeros(t.shape[:3] + t.shape[4:], dtype=t.dtype)
+    out[1:] += t[:-1, :, :, 0]
+    out[:-1] -= t[:-1, :, :, 0]
+    out[:, 1:] += t[:, :-1, :, 1]
+    out[:, :-1] -= t[:, :-1, :, 1]
+    out[:, :, 1:] += t[:, :, :-1, 2]
+    out[:, :, :-1] -= t[:, :, :-1, 2]
+    return out
+
+
 def dwt_coarse_box(dims, wavelet, levels):
     """the coarse (approximation) box that `dwt_plan` leaves: the part of the coefficients soft_threshold keeps"""
     return dwt_plan(dims, wavelet, levels)[1]
@@ -446,6 +468,10 @@ class Backend(object):
         """the unitary wavelet transform of an F-ordered `dims` volume (see operators.Wavelet); .H is its inverse"""
         return op.Wavelet(self, dims, wavelet=wavelet, levels=levels, **kwargs)
 
+    def Gradient(self, dims, **kwargs):
+        """the forward-difference gradient of an F-ordered `dims` volume, shape (3N, N) (see operators.Gradient); .H is its adjoint"""
+        return op.Gradient(self, dims, **kwargs)
+
     def Interp(self, N, coord, width, table, dtype=_C64, **kwargs):
         """gridding / interpolation matrix (npts x prod N) from a k-space trajectory"""
         assert len(N) == 3
@@ -599,6 +625,42 @@ class Backend(object):
         inside[tuple(slice(0, int(c)) for c in keep)] = True
         out = np.where(inside[..., None], v, (out * f).astype(_C64))
         x.copy_from(np.asfortranarray(out.astype(_C64).reshape(x.shape, order='F')))
+
+    def grad3(self, y, x, dims, adjoint=False, alpha=1, beta=0):
+        """y[:, j] = beta*y[:, j] + alpha * D x[:, j] (adjoint: D^H x[:, j]) for every column j.  D is the forward difference of an
+        F-ordered `dims` volume of N voxels along its three axes, zero at the far face: (D_a x)[i] = x[i + e_a] - x[i] where
+        i_a < n_a - 1, component a in rows [aN, (a+1)N) of a 3N-row column.  beta == 0: y is not read; y must not
+        overlap x.  This host form computes in float64 through to_host / copy_from, so that every backend has it; device
+        backends override it."""
+        dims = tuple(int(n) for n in dims)
+        n = int(np.prod(dims))
+        rows_x, rows_y = (3 * n, n) if adjoint else (n, 3 * n)
+        assert x.size % rows_x == 0 and x.size // rows_x * rows_y == y.size, (x.shape, y.shape, dims)
+        ncols = x.size // rows_x
+        if adjoint:
+            out = _grad_adjoint(x.to_host().reshape(dims + (3, ncols), order='F').astype(np.complex128))
+        else:
+            out = _grad_forward(x.to_host().reshape(dims + (ncols,), order='F').astype(np.complex128))
+        out = out.reshape((rows_y, ncols), order='F') * complex(alpha)
+        if beta != 0:
+            out = out + complex(beta) * y.to_host().reshape((rows_y, ncols), order='F')
+        y.copy_from(np.asfortranarray(out.astype(_C64).reshape(y.shape, order='F')))
+
+    def tv_dual_step(self, u, xn, xo, sigma, mu, dims):
+        """u <- proj_mu(u + sigma * D(2*xn - xo)) in place, column by column: the dual step of isotropic total variation.  proj_mu
+        scales the three components of u at a voxel by (r <= mu ? 1 : mu / r), r = sqrt(sum_a |u_a[i]|^2).  Host form in float64
+        through to_host / copy_from; device backends override it."""
+        dims = tuple(int(n) for n in dims)
+        n = int(np.prod(dims))
+        assert xn.size % n == 0 and xn.size == xo.size and u.size == 3 * xn.size and mu >= 0, (u.shape, xn.shape, xo.shape, dims, mu)
+        ncols = xn.size // n
+        w = 2.0 * xn.to_host().astype(np.complex128) - xo.to_host().astype(np.complex128)
+        t = u.to_host().reshape(dims + (3, ncols), order='F').astype(np.complex128)
+        t = t + float(sigma) * _grad_forward(w.reshape(dims + (ncols,), order='F'))
+        r = np.sqrt((t.real ** 2 + t.imag ** 2).sum(axis=3, keepdims=True))
+        with np.errstate(divide='ignore', invalid='ignore'):
+            f = np.where(r <= float(mu), 1.0, float(mu) / r)
+        u.copy_from(np.asfortranarray((t * f).astype(_C64).reshape(u.shape, order='F')))
 
     def supports_padded_fft(self, grid, ncoils=None):
         """whether `fft_padded` / `ifft_cropped[_sum]` exist for this oversampled grid (and, if given, this many coils)"""
@@ -808,6 +870,38 @@ class Backend(object):
             self.axpby(-m, x, 1 + m, g)                # x_k's buffer <- z_{k+1}
             x, z, g = g, x, z
             t = t_next
+            if callback is not None:
+                callback(k, x)
+        if x is not x_out:
+            x_out.copy(x)
+        if not in_place:
+            x_out.copy_to(x_h)
+
+    def primal_dual(self, gradf, proxg, KH, dual_step, tau, x_h, u, maxiter=100, callback=None):
+        """The Condat-Vu primal-dual iteration with an explicit gradient step, for min_x f(x) + g(x) + h(K x) with f smooth:
+
+            x_{k+1} = prox_{tau g}( x_k - tau (grad f(x_k) + K^H u_k) ),
+            u_{k+1} = dual_step(u_k, x_{k+1}, x_k)          # = prox_{sigma h*}(u_k + sigma K (2 x_{k+1} - x_k))
+
+        gradf(g, x) writes grad f(x) into g; KH(g, u) adds K^H u onto g; proxg(v, tau) replaces v by prox_{tau g}(v), or is None
+        (g = 0); dual_step(u, xn, xo) updates the dual variable u in place.  It converges for 1/tau - sigma ||K||^2 >= L/2, L the
+        Lipschitz constant of grad f (Condat 2013, Vu 2013).  x_h is the start and receives the result (a host array, or a device
+        array of this backend, updated in place); u is a device array, the dual start, updated in place.  callback(k, x), when
+        given, runs after iteration k (from 0) with the iterate x_{k+1}.  Two primal vectors: the gradient is built in g's
+        buffer, one axpby turns it into x_{k+1} there, and after the dual step x_k's buffer is free to be the next g -- the
+        two change roles as in `fista`.  On a device backend an iteration enqueues work and never waits for the device."""
+        in_place = isinstance(x_h, self.dndarray)
+        x = x_h if in_place else self.copy_array(x_h, name='x')
+        x_out = x
+        g = x.copy(name='g')
+        for k in range(int(maxiter)):
+            gradf(g, x)
+            KH(g, u)
+            self.axpby(-tau, g, 1, x)                  # g <- x_k - tau (grad f(x_k) + K^H u_k)
+            if proxg is not None:
+                proxg(g, tau)                          # g <- x_{k+1}
+            dual_step(u, g, x)
+            x, g = g, x
             if callback is not None:
                 callback(k, x)
         if x is not x_out:

@@ -817,6 +817,31 @@ class HipBackend(Backend):
         self._check(self._L.ig_csoft_c64(self._ctx, n0, n1, n2, c0, c1, c2, ncols, ctypes.c_float(float(tau)),
                                          ctypes.c_void_p(x._arr), x._leading_dim), "ig_csoft_c64")
 
+    def grad3(self, y, x, dims, adjoint=False, alpha=1, beta=0):
+        """Backend.grad3 on the device (ig_grad3_c64 / ig_grad3h_c64): panels of any column count with their leading dimensions"""
+        assert x.dtype == _C64 and y.dtype == _C64, "only complex64 is supported"
+        n0, n1, n2 = (int(n) for n in dims)
+        n = n0 * n1 * n2
+        rows_x, rows_y = (3 * n, n) if adjoint else (n, 3 * n)
+        assert x.shape[0] == rows_x and y.shape[0] == rows_y and x.size // rows_x == y.size // rows_y, (x.shape, y.shape, dims)
+        ncols = x.shape[1] if x.ndim == 2 else 1
+        ar, ai = _cplx(alpha)
+        br, bi = _cplx(beta)
+        name = "ig_grad3h_c64" if adjoint else "ig_grad3_c64"
+        self._check(getattr(self._L, name)(self._ctx, n0, n1, n2, ncols, ctypes.c_void_p(x._arr), x._leading_dim, ar, ai, br, bi,
+                                           ctypes.c_void_p(y._arr), y._leading_dim), name)
+
+    def tv_dual_step(self, u, xn, xo, sigma, mu, dims):
+        """Backend.tv_dual_step on the device (ig_tv_dual_c64), in place on u"""
+        assert u.dtype == _C64 and xn.dtype == _C64 and xo.dtype == _C64, "only complex64 is supported"
+        n0, n1, n2 = (int(n) for n in dims)
+        n = n0 * n1 * n2
+        assert xn.shape[0] == n and xo.shape == xn.shape and u.shape[0] == 3 * n and u.size == 3 * xn.size, (u.shape, xn.shape, xo.shape, dims)
+        ncols = xn.shape[1] if xn.ndim == 2 else 1
+        self._check(self._L.ig_tv_dual_c64(self._ctx, n0, n1, n2, ncols, ctypes.c_void_p(xn._arr), xn._leading_dim,
+                                           ctypes.c_void_p(xo._arr), xo._leading_dim, ctypes.c_float(float(sigma)),
+                                           ctypes.c_float(float(mu)), ctypes.c_void_p(u._arr), u._leading_dim), "ig_tv_dual_c64")
+
     def fftn(self, y, x):
         self._fft(y, x, -1)
 

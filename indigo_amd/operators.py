@@ -544,6 +544,29 @@ class Wavelet(MatrixFreeOperator):
         self._backend.dwt3(y, x, self._dims, self._wavelet, self._levels, inverse=not forward, alpha=alpha, beta=beta)
 
 
+class Gradient(MatrixFreeOperator):
+    """The forward-difference gradient D of an F-ordered complex64 volume of shape `dims` with N voxels (2-D: dims[2] == 1), shape
+    (3N, N): (D_a x)[i] = x[i + e_a] - x[i] where i_a < n_a - 1 and 0 on the far face, component a in rows [aN, (a+1)N); an
+    axis of length 1 contributes nothing.  .H is the adjoint (minus the divergence); ||D||^2 <= 4 per axis longer than 1.
+    The analysis operator of pics --tv."""
+
+    def __init__(self, backend, dims, **kwargs):
+        self._dims = tuple(int(n) for n in dims)
+        if len(self._dims) != 3 or min(self._dims) < 1:
+            raise ValueError("Gradient: dims must be three positive lengths, got %s" % (dims,))
+        n = int(np.prod(self._dims))
+        kwargs.setdefault('name', 'gradient')
+        super().__init__(backend, shape=(3 * n, n), **kwargs)
+
+    def _eval(self, y, x, alpha=1, beta=0, forward=True, left=True):
+        trace = getattr(self._backend, 'trace', None)
+        if trace is not None:
+            # either way one volume and three components move (32 B per voxel); beta != 0 reads the output as well
+            trace.add('gradient', nbytes=32 * self.shape[1] * x.shape[1] + (0 if beta == 0 else y.nbytes), nflops=0,
+                      shape=x.shape, forward=forward, name=self._name)
+        self._backend.grad3(y, x, self._dims, adjoint=not forward, alpha=alpha, beta=beta)
+
+
 class Eye(MatrixFreeOperator):
     def __init__(self, backend, n, **kwargs):
         super().__init__(backend, shape=(n, n), **kwargs)

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Parallel-imaging reconstruction driver: non-Cartesian SENSE by conjugate gradients.
+"""Parallel-imaging reconstruction driver: non-Cartesian SENSE by conjugate gradients, L1-wavelet FISTA or total-variation primal-dual.
 
     python -m indigo_amd.pics [-i ITER] [--lamda L] [-O LEVEL] [--crop "COIL:2,TIME:1"] [--no-fuse] scan.h5 | scan.npz
     python -m indigo_amd.pics --l1 LAMBDA [--wavelet db2] [--levels 3] [--step S | --power-iters 15] ... scan.npz
+    python -m indigo_amd.pics --tv MU [--tv-sigma S] [--l1 LAMBDA ...] [--step S | --power-iters 15] ... scan.npz
 
 The counterpart of the reference's driver script (examples/pics.py:20-95 arguments, data layout and tree
 construction, :179-233 recipe, normal equations, CG, output): reads `data` (k-space), `maps` (coil sensitivities)
@@ -20,6 +21,13 @@ With `--l1 LAMBDA > 0` (compressed sensing, no counterpart in the reference's dr
 
 by `Backend.fista` on the same A and the same normalised A^H y, with the fixed step 0.9 / (largest eigenvalue of
 A^H A + lamda I, from `--power-iters` power iterations) unless `--step` gives one.
+
+With `--tv MU > 0` (total variation, `bart pics -R T`; no counterpart in the reference's driver either) it solves
+
+    min_x  1/2 ||A x - y||^2 + lamda/2 ||x||^2 + MU sum_i ||(D x)_i||_2   [ + LAMBDA ||W x||_1  when --l1 is also given ]
+
+(D: operators.Gradient, forward differences; isotropic: the 2-norm of the three complex differences at a voxel) by
+`Backend.primal_dual` (Condat-Vu) on the same A and normalised A^H y, with the steps of `tv_solve`.
 
 Containers: HDF5 (`.h5`, the reference's format; needs h5py, which this image does not ship) or NumPy `.npz` with
 the same three arrays in the same orientation; the result goes back into the HDF5 file as dataset `rec`, or next to
@@ -45,7 +53,7 @@ class dim:
 
 
 def parse(argv):
-    ap = argparse.ArgumentParser(prog="indigo_amd.pics", description="Parallel Imaging and Compressed Sensing (non-Cartesian SENSE: CG, or L1-wavelet FISTA).")
+    ap = argparse.ArgumentParser(prog="indigo_amd.pics", description="Parallel Imaging and Compressed Sensing (non-Cartesian SENSE: CG, L1-wavelet FISTA, or total-variation primal-dual).")
     ap.add_argument('-i', type=int, default=20, help='number of CG iterations')
     ap.add_argument('--backend', type=str, default='hip', choices=['hip'])
     ap.add_argument('--device', type=int, default=0)
@@ -61,6 +69,8 @@ def parse(argv):
     ap.add_argument('--levels', type=int, default=3, help='wavelet levels of --l1')
     ap.add_argument('--power-iters', type=int, default=15, help='power iterations that estimate the FISTA step')
     ap.add_argument('--step', type=float, default=None, help='FISTA step (default 0.9 / the power-iteration estimate)')
+    ap.add_argument('--tv', type=float, default=0, help='total-variation weight; > 0 solves by the primal-dual iteration (0: off)')
+    ap.add_argument('--tv-sigma', type=float, default=None, help='dual step of --tv (default L / 24, L = 0.9 / the primal step)')
     ap.add_argument('data', nargs='?', default="scan.h5", help='k-space data: HDF5 (data/maps/traj) or .npz')
     return ap.parse_args(argv)
 
@@ -114,6 +124,15 @@ def power_iteration(B, AHA, iters, seed=0):
     return lam
 
 
+def wavelet_prox(B, W, dims, l1):
+    """proxg(v, alpha) of l1 ||W v||_1 (W's coarse band excluded): v <- W^H soft_{alpha l1}(W v), in place (W is unitary)"""
+    def proxg(v, alpha):
+        W.eval(v, v)
+        B.soft_threshold(v, alpha * l1, dims, W.coarse)
+        W.H.eval(v, v)
+    return proxg
+
+
 def fista_solve(B, AHA, AHy, dims, iters, l1, wavelet='db2', levels=3, power_iters=15, step=None, ynorm2=0.0):
     """min_x 1/2 x^H AHA x - Re(x^H AHy) + ynorm2 / 2 + l1 ||W x||_1 (W's coarse band excluded) by Backend.fista from x = 0;
     with AHA = A^H A + lamda I and AHy = A^H y that is 1/2 ||A x - y||^2 + lamda/2 ||x||^2 + l1 ||W x||_1 for ynorm2 = ||y||^2.
@@ -134,11 +153,7 @@ def fista_solve(B, AHA, AHy, dims, iters, l1, wavelet='db2', levels=3, power_ite
         AHA.eval(g, z)
         B.axpby(1, g, -1, b)
 
-    def proxg(v, alpha):
-        W.eval(v, v)
-        B.soft_threshold(v, alpha * l1, dims, W.coarse)
-        W.H.eval(v, v)
-
+    proxg = wavelet_prox(B, W, dims, l1)
     objectives = []
     work = {}
 
@@ -164,10 +179,78 @@ def fista_solve(B, AHA, AHy, dims, iters, l1, wavelet='db2', levels=3, power_ite
     return x, objectives
 
 
+def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', levels=3, power_iters=15, step=None, ynorm2=0.0):
+    """min_x 1/2 x^H AHA x - Re(x^H AHy) + ynorm2 / 2 + mu sum_i ||(D x)_i||_2 [+ l1 ||W x||_1] by Backend.primal_dual from x = 0,
+    u = 0: with AHA = A^H A + lamda I and AHy = A^H y that is 1/2 ||A x - y||^2 + lamda/2 ||x||^2 + mu TV(x) [+ l1 ||W x||_1] for
+    ynorm2 = ||y||^2.  D is operators.Gradient; the dual step is u <- proj_mu(u + sigma D(2 x_{k+1} - x_k)), the projection onto
+    the 2-norm ball of radius mu at every voxel (Backend.tv_dual_step); proxg is `wavelet_prox` when l1 > 0, else the identity.
+
+    Steps: L is the largest eigenvalue of AHA (`power_iteration`), or 0.9 / step when `step` is given; tau = 0.9 / L and
+    sigma = L / 24 unless given.  With ||D||^2 <= 12:  1/tau - 12 sigma = L/0.9 - L/2 = 0.61 L >= L/2, the Condat-Vu condition.
+    Returns the image as a host (N, 1) array and the objectives logged: [(iteration, value)], every 10 iterations and the last."""
+    c64 = np.dtype('complex64')
+    G = B.Gradient(dims)
+    if step is None:
+        L = power_iteration(B, AHA, power_iters)
+        log.info("tv: largest eigenvalue of A^H A + lamda I %.6e (%d power iterations)", L, power_iters)
+    else:
+        L = 0.9 / step
+    tau = 0.9 / L
+    if sigma is None:
+        sigma = L / 24
+    log.info("tv: tau %.6e, sigma %.6e, mu %g, %s", tau, sigma, mu, tuple(dims))
+    W = proxg = None
+    if l1 > 0:
+        W = B.Wavelet(dims, wavelet=wavelet, levels=levels)
+        proxg = wavelet_prox(B, W, dims, l1)
+        log.info("tv: %s wavelet, %d levels, coarse box %s, l1 %g", wavelet, levels, W.coarse, l1)
+    n = AHA.shape[1]
+    b = B.copy_array(AHy, name='AHy')
+    u = B.zero_array((3 * n, 1), c64, name='tv.u')
+
+    def gradf(g, z):
+        AHA.eval(g, z)
+        B.axpby(1, g, -1, b)
+
+    def KH(g, v):
+        G.eval(g, v, alpha=1, beta=1, forward=False)
+
+    def dual_step(v, xn, xo):
+        B.tv_dual_step(v, xn, xo, sigma, mu, dims)
+
+    objectives = []
+    work = {}
+
+    def objective(k, x):
+        if not (k % 10 == 9 or k == iters - 1) or not log.isEnabledFor(logging.INFO):
+            return
+        if not work:
+            work['q'] = B.zero_array((n, 1), c64, name='objective.q')
+            work['d'] = B.zero_array((3 * n, 1), c64, name='objective.d')
+        q, d = work['q'], work['d']
+        AHA.eval(q, x)
+        G.eval(d, x)
+        diffs = d.to_host().reshape((n, 3), order='F').astype(np.complex128)
+        val = 0.5 * B.dot(x, q) - B.dot(x, b) + 0.5 * ynorm2 + mu * float(np.sqrt((np.abs(diffs) ** 2).sum(axis=1)).sum())
+        if W is not None:
+            W.eval(q, x)
+            coef = q.to_host().reshape(tuple(dims), order='F')
+            inside = np.zeros(tuple(dims), dtype=bool)
+            inside[tuple(slice(0, c) for c in W.coarse)] = True
+            val += l1 * float(np.abs(coef[~inside].astype(np.complex128)).sum())
+        objectives.append((k + 1, val))
+        log.info("tv iter %d, objective %.9e", k + 1, val)
+
+    x = np.zeros((n, 1), dtype=c64, order='F')
+    B.primal_dual(gradf, proxg, KH, dual_step, tau, x, u, maxiter=iters, callback=objective)
+    return x, objectives
+
+
 def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, width=3, fuse=True,
-                l1=0.0, wavelet='db2', levels=3, power_iters=15, step=None):
+                l1=0.0, wavelet='db2', levels=3, power_iters=15, step=None, tv=0.0, tv_sigma=None):
     """ksp: (1, readout, views, C, 1, ...), mps: (X, Y, Z, C, 1), traj: (3, readout, views) in pixels -> image (X, Y, Z, 1, ...)
-    l1 > 0: L1-wavelet regularised by FISTA (`fista_solve`), else CG on the normal equations"""
+    tv > 0: total-variation regularised by the primal-dual iteration (`tv_solve`; with l1 > 0 the wavelet term as well);
+    l1 > 0: L1-wavelet regularised by FISTA (`fista_solve`); else CG on the normal equations"""
     from indigo_amd.transforms import FuseZpadFFT, Optimize, sense_recipe
     from indigo_amd.transforms import reserve_for
     ksp = np.asarray(ksp, dtype=np.complex64)
@@ -201,8 +284,13 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
     AHy = A.H * y
     scale = abs(AHy).max()
     AHy /= scale
-    if l1 > 0:
+    if tv > 0 or l1 > 0:
         ynorm2 = float(np.vdot(y, y).real) / float(scale) ** 2          # the data term of the same normalised problem
+    if tv > 0:
+        x, _ = tv_solve(B, AHA, AHy, mps.shape[:3], iters, tv, sigma=tv_sigma, l1=l1, wavelet=wavelet, levels=levels,
+                        power_iters=power_iters, step=step, ynorm2=ynorm2)
+        return x.reshape(img_dims, order='F')
+    if l1 > 0:
         x, _ = fista_solve(B, AHA, AHy, mps.shape[:3], iters, l1, wavelet=wavelet, levels=levels, power_iters=power_iters,
                            step=step, ynorm2=ynorm2)
         return x.reshape(img_dims, order='F')
@@ -226,7 +314,7 @@ def main(argv=None, backend=None):
     trj = traj[tuple(slice(0, min(n, c)) for n, c in zip(traj.shape, crops[-traj.ndim:]))].T
     img = reconstruct(backend, ksp, mps, trj, iters=args.i, lamda=args.lamda, level=args.recipe, osf=args.osf,
                       width=args.width, fuse=not args.no_fuse, l1=args.l1, wavelet=args.wavelet, levels=args.levels,
-                      power_iters=args.power_iters, step=args.step)
+                      power_iters=args.power_iters, step=args.step, tv=args.tv, tv_sigma=args.tv_sigma)
     write(img.T)
     log.info("reconstruction complete")
     return img
