@@ -210,6 +210,24 @@ int  ig_grad3h_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t ncol
  * three components are scaled by (r <= mu ? 1 : mu / r).  mu >= 0; u must overlap neither xn nor xo (xn may be xo).         */
 int  ig_tv_dual_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t ncols, const void* xn, int64_t ldxn,
                     const void* xo, int64_t ldxo, float sigma, float mu, void* u, int64_t ldu);
+/* The same three with a fourth difference along the columns of the panel, the nt time frames (operators.GradientT,
+ * Backend.grad4 / tv4_dual_step, pics --tv-time).  x is N x nt, u is 4N x nt: components 0..2 of column t are
+ * D x[:, t] as above, component 3 (rows [3N, 4N)) is x[:, t+1] - x[:, t] for t < nt-1 and 0 for t = nt-1.
+ * ig_grad4_c64:   y[:, t] = beta*y[:, t] + alpha * (D4 x)[:, t]                         (y: 4N x nt, ldy >= 4N; x: N x nt)
+ * ig_grad4h_c64:  y[:, t] = beta*y[:, t] + alpha * (D^H u_{0..2}[:, t] + (t > 0 ? u_3[:, t-1] : 0) - (t < nt-1 ? u_3[:, t] : 0))
+ *                 (y: N x nt; u: 4N x nt; u_3 of the last frame is never read)
+ * beta == 0: y is not read.  An output panel that overlaps an input panel is IG_ERR_ARG.  With nt == 1 the results are those
+ * of the 3-D entries with a zero fourth component.  Bytes per voxel and frame, f = (nt-1)/nt (the neighbouring frame is 8*ld
+ * bytes away and is read from memory again): grad4 40 + 8f (+ 32 when beta != 0), grad4h 32 + 16f (+ 8), tv4_dual 80 + 16f.   */
+int  ig_grad4_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t nt, const void* x, int64_t ldx,
+                  float alpha_re, float alpha_im, float beta_re, float beta_im, void* y, int64_t ldy);
+int  ig_grad4h_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t nt, const void* u, int64_t ldu,
+                   float alpha_re, float alpha_im, float beta_re, float beta_im, void* y, int64_t ldy);
+/* u <- proj(u + sigma * D4(2*xn - xo)) in place, one pass: per voxel and frame components 0..2 are scaled by
+ * (r <= mu ? 1 : mu / r), r = sqrt(sum_{a<3} |u_a[i]|^2), and component 3 by (|u_3| <= mu_t ? 1 : mu_t / |u_3|), a constraint
+ * of its own.  mu, mu_t >= 0 (0 gives exact zeros in that part); u must overlap neither xn nor xo (xn may be xo).             */
+int  ig_tv4_dual_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t nt, const void* xn, int64_t ldxn,
+                     const void* xo, int64_t ldxo, float sigma, float mu, float mu_t, void* u, int64_t ldu);
 
 /* ------------------------------------------------------------------------
  * CSR x dense-panel SpMM.  Replaces Backend.ccsrmm

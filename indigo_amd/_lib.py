@@ -76,6 +76,12 @@ PROTOTYPES = {
                                    c_float, c_float, c_float, c_float, c_void_p, c_int64]),
     "ig_tv_dual_c64":     (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                    c_float, c_float, c_void_p, c_int64]),
+    "ig_grad4_c64":       (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64,
+                                   c_float, c_float, c_float, c_float, c_void_p, c_int64]),
+    "ig_grad4h_c64":      (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64,
+                                   c_float, c_float, c_float, c_float, c_void_p, c_int64]),
+    "ig_tv4_dual_c64":    (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                   c_float, c_float, c_float, c_void_p, c_int64]),
     "ig_ccsrmm_il":       (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64,
                                    c_float, c_float, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_float, c_float, c_void_p, c_int64]),

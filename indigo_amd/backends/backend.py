@@ -181,6 +181,12 @@ class Backend(object):
             ld = new_shape[0] if new_shape[0] < self.shape[0] else self._leading_dim
             return self._view(new_shape, ld, self._arr)
 
+        def dense_rows(self, start, stop):
+            """rows [start, stop) of every column, as `a[start:stop, :]` gives them; of a one-column array the view is a contiguous
+            vector (leading dimension = its length) whatever the parent's leading dimension is"""
+            v = self[slice(start, stop), :]
+            return v._view(v.shape, v.shape[0], v._arr) if v.shape[1] == 1 else v
+
         def _view(self, shape, ld, data):
             v = self._backend.dndarray(self._backend, shape, self.dtype, ld=ld, own=False, data=data)
             v._base = getattr(self, '_base', None) or self     # keep the owner alive
@@ -472,6 +478,11 @@ class Backend(object):
         """the forward-difference gradient of an F-ordered `dims` volume, shape (3N, N) (see operators.Gradient); .H is its adjoint"""
         return op.Gradient(self, dims, **kwargs)
 
+    def GradientT(self, dims, frames, **kwargs):
+        """the gradient of `frames` time frames of a `dims` volume with the forward difference between neighbouring frames as a
+        fourth component, shape (4NT, NT) (see operators.GradientT); .H is its adjoint"""
+        return op.GradientT(self, dims, frames, **kwargs)
+
     def Interp(self, N, coord, width, table, dtype=_C64, **kwargs):
         """gridding / interpolation matrix (npts x prod N) from a k-space trajectory"""
         assert len(N) == 3
@@ -661,6 +672,53 @@ class Backend(object):
         with np.errstate(divide='ignore', invalid='ignore'):
             f = np.where(r <= float(mu), 1.0, float(mu) / r)
         u.copy_from(np.asfortranarray((t * f).astype(_C64).reshape(u.shape, order='F')))
+
+    def grad4(self, y, x, dims, frames, adjoint=False, alpha=1, beta=0):
+        """y = beta*y + alpha * D4 x (adjoint: D4^H x) for T = `frames` time frames of an F-ordered `dims` volume of N voxels.  x is
+        the N x T panel of the frames, or the same as an (N T, 1) vector, frame t in rows [tN, (t+1)N); D4 x is 4N x T, or
+        (4N T, 1): components 0..2 of frame t are D x_t as in `grad3`, component 3 (rows [3N, 4N) of the frame's 4N) is
+        x_{t+1} - x_t for t < T - 1 and 0 in the last frame.  (D4^H u)_t = D^H u_{0..2, t} + (t > 0 ? u_{3, t-1} : 0) -
+        (t < T - 1 ? u_{3, t} : 0): u_3 of the last frame is not read.  beta == 0: y is not read; y must not
+        overlap x.  Host form in float64 through to_host / copy_from; device backends override it."""
+        dims = tuple(int(n) for n in dims)
+        n, T = int(np.prod(dims)), int(frames)
+        rows_x, rows_y = (4 * n, n) if adjoint else (n, 4 * n)
+        assert T >= 1 and x.size == rows_x * T and y.size == rows_y * T, (x.shape, y.shape, dims, frames)
+        if adjoint:
+            t = x.to_host().reshape(dims + (4, T), order='F').astype(np.complex128)
+            out = _grad_adjoint(t[:, :, :, :3])
+            out[..., 1:] += t[:, :, :, 3, :-1]
+            out[..., :-1] -= t[:, :, :, 3, :-1]
+        else:
+            v = x.to_host().reshape(dims + (T,), order='F').astype(np.complex128)
+            out = np.zeros(dims + (4, T), dtype=np.complex128)
+            out[:, :, :, :3] = _grad_forward(v)
+            out[:, :, :, 3, :-1] = v[..., 1:] - v[..., :-1]
+        out = out.reshape((rows_y, T), order='F') * complex(alpha)
+        if beta != 0:
+            out = out + complex(beta) * y.to_host().reshape((rows_y, T), order='F')
+        y.copy_from(np.asfortranarray(out.astype(_C64).reshape(y.shape, order='F')))
+
+    def tv4_dual_step(self, u, xn, xo, sigma, mu, mu_t, dims, frames):
+        """u <- proj(u + sigma * D4(2*xn - xo)) in place: the dual step of spatial plus temporal total variation on `frames` time
+        frames (layouts as in `grad4`).  Per voxel and frame the three spatial components are scaled onto the 2-norm ball of
+        radius mu, as `tv_dual_step` does, and the temporal component onto the disc |u_3| <= mu_t, a constraint of its own.
+        Host form in float64 through to_host / copy_from; device backends override it."""
+        dims = tuple(int(n) for n in dims)
+        n, T = int(np.prod(dims)), int(frames)
+        assert T >= 1 and xn.size == n * T and xo.size == n * T and u.size == 4 * n * T and mu >= 0 and mu_t >= 0, \
+            (u.shape, xn.shape, xo.shape, dims, frames, mu, mu_t)
+        w = 2.0 * xn.to_host().astype(np.complex128) - xo.to_host().astype(np.complex128)
+        w = w.reshape(dims + (T,), order='F')
+        t = u.to_host().reshape(dims + (4, T), order='F').astype(np.complex128)
+        t[:, :, :, :3] += float(sigma) * _grad_forward(w)
+        t[:, :, :, 3, :-1] += float(sigma) * (w[..., 1:] - w[..., :-1])
+        r = np.sqrt((t.real ** 2 + t.imag ** 2)[:, :, :, :3].sum(axis=3, keepdims=True))
+        rt = np.abs(t[:, :, :, 3:])
+        with np.errstate(divide='ignore', invalid='ignore'):
+            t[:, :, :, :3] *= np.where(r <= float(mu), 1.0, float(mu) / r)
+            t[:, :, :, 3:] *= np.where(rt <= float(mu_t), 1.0, float(mu_t) / rt)
+        u.copy_from(np.asfortranarray(t.astype(_C64).reshape(u.shape, order='F')))
 
     def supports_padded_fft(self, grid, ncoils=None):
         """whether `fft_padded` / `ifft_cropped[_sum]` exist for this oversampled grid (and, if given, this many coils)"""

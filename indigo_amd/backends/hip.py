@@ -842,6 +842,37 @@ class HipBackend(Backend):
                                            ctypes.c_void_p(xo._arr), xo._leading_dim, ctypes.c_float(float(sigma)),
                                            ctypes.c_float(float(mu)), ctypes.c_void_p(u._arr), u._leading_dim), "ig_tv_dual_c64")
 
+    @staticmethod
+    def _frame_panel(a, rows, frames):
+        """(pointer, leading dimension) of `a` as a rows x frames panel: a is that panel, or the (rows * frames, 1) vector"""
+        if a.shape == (rows, frames):
+            return ctypes.c_void_p(a._arr), a._leading_dim
+        assert a.shape in ((rows * frames, 1), (rows * frames,)), (a.shape, rows, frames)
+        return ctypes.c_void_p(a._arr), rows
+
+    def grad4(self, y, x, dims, frames, adjoint=False, alpha=1, beta=0):
+        """Backend.grad4 on the device (ig_grad4_c64 / ig_grad4h_c64): the frames are the columns of a panel with its leading
+        dimension, or stacked in one column"""
+        assert x.dtype == _C64 and y.dtype == _C64, "only complex64 is supported"
+        n0, n1, n2 = (int(n) for n in dims)
+        n, T = n0 * n1 * n2, int(frames)
+        rows_x, rows_y = (4 * n, n) if adjoint else (n, 4 * n)
+        (xp, ldx), (yp, ldy) = self._frame_panel(x, rows_x, T), self._frame_panel(y, rows_y, T)
+        ar, ai = _cplx(alpha)
+        br, bi = _cplx(beta)
+        name = "ig_grad4h_c64" if adjoint else "ig_grad4_c64"
+        self._check(getattr(self._L, name)(self._ctx, n0, n1, n2, T, xp, ldx, ar, ai, br, bi, yp, ldy), name)
+
+    def tv4_dual_step(self, u, xn, xo, sigma, mu, mu_t, dims, frames):
+        """Backend.tv4_dual_step on the device (ig_tv4_dual_c64), in place on u"""
+        assert u.dtype == _C64 and xn.dtype == _C64 and xo.dtype == _C64, "only complex64 is supported"
+        n0, n1, n2 = (int(n) for n in dims)
+        n, T = n0 * n1 * n2, int(frames)
+        (np_, ldn), (op_, ldo), (up, ldu) = (self._frame_panel(xn, n, T), self._frame_panel(xo, n, T),
+                                             self._frame_panel(u, 4 * n, T))
+        self._check(self._L.ig_tv4_dual_c64(self._ctx, n0, n1, n2, T, np_, ldn, op_, ldo, ctypes.c_float(float(sigma)),
+                                            ctypes.c_float(float(mu)), ctypes.c_float(float(mu_t)), up, ldu), "ig_tv4_dual_c64")
+
     def fftn(self, y, x):
         self._fft(y, x, -1)
 

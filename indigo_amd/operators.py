@@ -567,6 +567,39 @@ class Gradient(MatrixFreeOperator):
         self._backend.grad3(y, x, self._dims, adjoint=not forward, alpha=alpha, beta=beta)
 
 
+class GradientT(MatrixFreeOperator):
+    """The gradient D4 of T = `frames` time frames of an F-ordered complex64 volume of shape `dims` with N voxels, shape (4NT, NT).
+    The input is frame-major, frame t in rows [tN, (t+1)N); the output holds 4N rows per frame: components 0..2 are `Gradient`'s
+    D x_t, component 3 is the forward difference in time x_{t+1} - x_t, 0 in the last frame.  .H is the adjoint, which does not
+    read the temporal component of the last frame.  ||D4||^2 <= 4 * (axes longer than 1, time included) <= 16.  frames == 1 is
+    `Gradient` with a zero fourth component.  The analysis operator of pics --tv / --tv-time on several frames."""
+
+    def __init__(self, backend, dims, frames, **kwargs):
+        self._dims = tuple(int(n) for n in dims)
+        self._frames = int(frames)
+        if len(self._dims) != 3 or min(self._dims) < 1:
+            raise ValueError("GradientT: dims must be three positive lengths, got %s" % (dims,))
+        if self._frames < 1:
+            raise ValueError("GradientT: frames must be positive, got %s" % (frames,))
+        n = int(np.prod(self._dims)) * self._frames
+        kwargs.setdefault('name', 'gradient_t')
+        super().__init__(backend, shape=(4 * n, n), **kwargs)
+
+    def _eval(self, y, x, alpha=1, beta=0, forward=True, left=True):
+        trace = getattr(self._backend, 'trace', None)
+        if trace is not None:
+            # one volume and four components per frame (40 B per voxel, adjoint 32: the last frame's temporal component is
+            # not read) and the neighbouring frame again, T - 1 times (8 B, adjoint 16); beta != 0 reads the output as well
+            n, T = self.shape[1] // self._frames, self._frames
+            per_col = n * (T * 40 + (T - 1) * 8) if forward else n * (T * 32 + (T - 1) * 16)
+            trace.add('gradient_t', nbytes=per_col * x.shape[1] + (0 if beta == 0 else y.nbytes), nflops=0,
+                      shape=x.shape, forward=forward, name=self._name)
+        if x.shape[1] == 1:
+            return self._backend.grad4(y, x, self._dims, self._frames, adjoint=not forward, alpha=alpha, beta=beta)
+        for j in range(x.shape[1]):             # the frames become the columns of a panel inside: one product per column
+            self._backend.grad4(y[:, j:j + 1], x[:, j:j + 1], self._dims, self._frames, adjoint=not forward, alpha=alpha, beta=beta)
+
+
 class Eye(MatrixFreeOperator):
     def __init__(self, backend, n, **kwargs):
         super().__init__(backend, shape=(n, n), **kwargs)
@@ -742,7 +775,8 @@ class BlockDiag(CompositeOperator):
         yo = xo = 0
         for C in self._children:
             h, w = C.shape if forward else C.shape[::-1]
-            C.eval(_slice_rows(y, yo, yo + h), _slice_rows(x, xo, xo + w),
+            # (dense_rows: a child may be a leaf that takes contiguous vectors only -- the fused SENSE leaf)
+            C.eval(y.dense_rows(yo, yo + h), x.dense_rows(xo, xo + w),
                    alpha=alpha, beta=beta, forward=forward, left=left)
             yo += h
             xo += w

@@ -4,6 +4,7 @@
     python -m indigo_amd.pics [-i ITER] [--lamda L] [-O LEVEL] [--crop "COIL:2,TIME:1"] [--no-fuse] scan.h5 | scan.npz
     python -m indigo_amd.pics --l1 LAMBDA [--wavelet db2] [--levels 3] [--step S | --power-iters 15] ... scan.npz
     python -m indigo_amd.pics --tv MU [--tv-sigma S] [--l1 LAMBDA ...] [--step S | --power-iters 15] ... scan.npz
+    python -m indigo_amd.pics --tv-time MU_T [--tv MU] [--l1 LAMBDA ...] ... frames.npz         (a scan with several time frames)
 
 The counterpart of the reference's driver script (examples/pics.py:20-95 arguments, data layout and tree
 construction, :179-233 recipe, normal equations, CG, output): reads `data` (k-space), `maps` (coil sensitivities)
@@ -28,6 +29,18 @@ With `--tv MU > 0` (total variation, `bart pics -R T`; no counterpart in the ref
 
 (D: operators.Gradient, forward differences; isotropic: the 2-norm of the three complex differences at a voxel) by
 `Backend.primal_dual` (Condat-Vu) on the same A and normalised A^H y, with the steps of `tv_solve`.
+
+Time frames.  With T = the length of TIME > 1 the image is frame-major (frame t in rows [tN, (t+1)N) of the unknown),
+A = BlockDiag(A_t) with A_t built as above from frame t's trajectory (`traj` with a TIME axis of length T) or from the one
+trajectory that all frames share (no TIME axis, or length 1; frames with equal trajectories share one operator tree, built
+and uploaded once), the maps are those of every frame, and all three solvers run on the stacked vectors: CG solves the block
+system jointly, `--l1` and `--tv` act on every frame, and `--tv-time MU_T > 0` adds
+
+    MU_T sum_{t < T-1} sum_i |x_{t+1}[i] - x_t[i]|                       (`bart pics -R T:1024:0:MU_T`)
+
+the term that couples the frames: `tv_solve` then uses operators.GradientT, a dual variable of 4NT rows and
+`Backend.tv4_dual_step`, whose temporal component has its own constraint |u_3| <= MU_T.  The result keeps
+the TIME axis: (X, Y, Z, 1, ..., T).
 
 Containers: HDF5 (`.h5`, the reference's format; needs h5py, which this image does not ship) or NumPy `.npz` with
 the same three arrays in the same orientation; the result goes back into the HDF5 file as dataset `rec`, or next to
@@ -70,7 +83,8 @@ def parse(argv):
     ap.add_argument('--power-iters', type=int, default=15, help='power iterations that estimate the FISTA step')
     ap.add_argument('--step', type=float, default=None, help='FISTA step (default 0.9 / the power-iteration estimate)')
     ap.add_argument('--tv', type=float, default=0, help='total-variation weight; > 0 solves by the primal-dual iteration (0: off)')
-    ap.add_argument('--tv-sigma', type=float, default=None, help='dual step of --tv (default L / 24, L = 0.9 / the primal step)')
+    ap.add_argument('--tv-sigma', type=float, default=None, help='dual step of --tv (default L / 24, with several time frames L / 32; L = 0.9 / the primal step)')
+    ap.add_argument('--tv-time', type=float, default=0, help='weight of the total variation between neighbouring time frames (0: off; no effect on one frame)')
     ap.add_argument('data', nargs='?', default="scan.h5", help='k-space data: HDF5 (data/maps/traj) or .npz')
     return ap.parse_args(argv)
 
@@ -125,17 +139,29 @@ def power_iteration(B, AHA, iters, seed=0):
 
 
 def wavelet_prox(B, W, dims, l1):
-    """proxg(v, alpha) of l1 ||W v||_1 (W's coarse band excluded): v <- W^H soft_{alpha l1}(W v), in place (W is unitary)"""
+    """proxg(v, alpha) of l1 ||W v||_1 (W's coarse band excluded): v <- W^H soft_{alpha l1}(W v), in place (W is unitary); a v
+    of several frames stacked is the panel of its frames, and W and the threshold act on every column"""
+    n = int(np.prod(dims))
+
     def proxg(v, alpha):
         W.eval(v, v)
-        B.soft_threshold(v, alpha * l1, dims, W.coarse)
+        B.soft_threshold(v.reshape((n, -1)), alpha * l1, dims, W.coarse)
         W.H.eval(v, v)
     return proxg
+
+
+def wavelet_l1(coef, dims, coarse):
+    """sum |coef| outside the coarse box of every frame, in complex128; coef: the host (N T, 1) wavelet coefficients"""
+    coef = coef.reshape(tuple(dims) + (-1,), order='F')
+    inside = np.zeros(tuple(dims), dtype=bool)
+    inside[tuple(slice(0, c) for c in coarse)] = True
+    return float(np.abs(coef[~inside].astype(np.complex128)).sum())
 
 
 def fista_solve(B, AHA, AHy, dims, iters, l1, wavelet='db2', levels=3, power_iters=15, step=None, ynorm2=0.0):
     """min_x 1/2 x^H AHA x - Re(x^H AHy) + ynorm2 / 2 + l1 ||W x||_1 (W's coarse band excluded) by Backend.fista from x = 0;
     with AHA = A^H A + lamda I and AHy = A^H y that is 1/2 ||A x - y||^2 + lamda/2 ||x||^2 + l1 ||W x||_1 for ynorm2 = ||y||^2.
+    AHA of NT columns is T frames of the `dims` volume stacked: W and the threshold then act on every frame.
     Returns the image as a host (N, 1) array and the objectives logged: [(iteration, value)], every 10 iterations and the last."""
     c64 = np.dtype('complex64')
     W = B.Wavelet(dims, wavelet=wavelet, levels=levels)
@@ -166,11 +192,7 @@ def fista_solve(B, AHA, AHy, dims, iters, l1, wavelet='db2', levels=3, power_ite
         q, w = work['q'], work['w']
         AHA.eval(q, x)
         W.eval(w, x)
-        coef = w.to_host().reshape(tuple(dims), order='F')
-        inside = np.zeros(tuple(dims), dtype=bool)
-        inside[tuple(slice(0, c) for c in W.coarse)] = True
-        l1_term = float(np.abs(coef[~inside].astype(np.complex128)).sum())
-        val = 0.5 * B.dot(x, q) - B.dot(x, b) + 0.5 * ynorm2 + l1 * l1_term
+        val = 0.5 * B.dot(x, q) - B.dot(x, b) + 0.5 * ynorm2 + l1 * wavelet_l1(w.to_host(), dims, W.coarse)
         objectives.append((k + 1, val))
         log.info("fista iter %d, objective %.9e", k + 1, val)
 
@@ -179,7 +201,8 @@ def fista_solve(B, AHA, AHy, dims, iters, l1, wavelet='db2', levels=3, power_ite
     return x, objectives
 
 
-def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', levels=3, power_iters=15, step=None, ynorm2=0.0):
+def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', levels=3, power_iters=15, step=None, ynorm2=0.0,
+             frames=1, mu_t=0.0):
     """min_x 1/2 x^H AHA x - Re(x^H AHy) + ynorm2 / 2 + mu sum_i ||(D x)_i||_2 [+ l1 ||W x||_1] by Backend.primal_dual from x = 0,
     u = 0: with AHA = A^H A + lamda I and AHy = A^H y that is 1/2 ||A x - y||^2 + lamda/2 ||x||^2 + mu TV(x) [+ l1 ||W x||_1] for
     ynorm2 = ||y||^2.  D is operators.Gradient; the dual step is u <- proj_mu(u + sigma D(2 x_{k+1} - x_k)), the projection onto
@@ -187,9 +210,17 @@ def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', le
 
     Steps: L is the largest eigenvalue of AHA (`power_iteration`), or 0.9 / step when `step` is given; tau = 0.9 / L and
     sigma = L / 24 unless given.  With ||D||^2 <= 12:  1/tau - 12 sigma = L/0.9 - L/2 = 0.61 L >= L/2, the Condat-Vu condition.
+
+    frames = T > 1: x is T frames stacked, frame t in rows [tN, (t+1)N), and the penalty is mu sum_t TV(x_t) + mu_t sum_{t<T-1}
+    sum_i |x_{t+1}[i] - x_t[i]| (the wavelet term on every frame).  D is operators.GradientT, u has 4NT rows, the dual step is
+    Backend.tv4_dual_step: the spatial components onto the ball of radius mu, the temporal one onto the disc of radius mu_t.
+    With ||D4||^2 <= 16 the default sigma is L / 32:  1/tau - 16 sigma = L/0.9 - L/2 >= L/2, the same margin.  frames = 1 is
+    the iteration above unchanged (mu_t does not enter).
     Returns the image as a host (N, 1) array and the objectives logged: [(iteration, value)], every 10 iterations and the last."""
     c64 = np.dtype('complex64')
-    G = B.Gradient(dims)
+    T = int(frames)
+    comps = 3 if T == 1 else 4
+    G = B.Gradient(dims) if T == 1 else B.GradientT(dims, T)
     if step is None:
         L = power_iteration(B, AHA, power_iters)
         log.info("tv: largest eigenvalue of A^H A + lamda I %.6e (%d power iterations)", L, power_iters)
@@ -197,8 +228,10 @@ def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', le
         L = 0.9 / step
     tau = 0.9 / L
     if sigma is None:
-        sigma = L / 24
+        sigma = L / (8 * comps)
     log.info("tv: tau %.6e, sigma %.6e, mu %g, %s", tau, sigma, mu, tuple(dims))
+    if T > 1:
+        log.info("tv: %d frames, mu_t %g", T, mu_t)
     W = proxg = None
     if l1 > 0:
         W = B.Wavelet(dims, wavelet=wavelet, levels=levels)
@@ -206,7 +239,7 @@ def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', le
         log.info("tv: %s wavelet, %d levels, coarse box %s, l1 %g", wavelet, levels, W.coarse, l1)
     n = AHA.shape[1]
     b = B.copy_array(AHy, name='AHy')
-    u = B.zero_array((3 * n, 1), c64, name='tv.u')
+    u = B.zero_array((comps * n, 1), c64, name='tv.u')
 
     def gradf(g, z):
         AHA.eval(g, z)
@@ -216,7 +249,10 @@ def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', le
         G.eval(g, v, alpha=1, beta=1, forward=False)
 
     def dual_step(v, xn, xo):
-        B.tv_dual_step(v, xn, xo, sigma, mu, dims)
+        if T == 1:
+            B.tv_dual_step(v, xn, xo, sigma, mu, dims)
+        else:
+            B.tv4_dual_step(v, xn, xo, sigma, mu, mu_t, dims, T)
 
     objectives = []
     work = {}
@@ -226,18 +262,17 @@ def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', le
             return
         if not work:
             work['q'] = B.zero_array((n, 1), c64, name='objective.q')
-            work['d'] = B.zero_array((3 * n, 1), c64, name='objective.d')
+            work['d'] = B.zero_array((comps * n, 1), c64, name='objective.d')
         q, d = work['q'], work['d']
         AHA.eval(q, x)
         G.eval(d, x)
-        diffs = d.to_host().reshape((n, 3), order='F').astype(np.complex128)
-        val = 0.5 * B.dot(x, q) - B.dot(x, b) + 0.5 * ynorm2 + mu * float(np.sqrt((np.abs(diffs) ** 2).sum(axis=1)).sum())
+        diffs = d.to_host().reshape((n // T, comps, T), order='F').astype(np.complex128)
+        val = 0.5 * B.dot(x, q) - B.dot(x, b) + 0.5 * ynorm2 + mu * float(np.sqrt((np.abs(diffs[:, :3]) ** 2).sum(axis=1)).sum())
+        if T > 1:
+            val += mu_t * float(np.abs(diffs[:, 3]).sum())
         if W is not None:
             W.eval(q, x)
-            coef = q.to_host().reshape(tuple(dims), order='F')
-            inside = np.zeros(tuple(dims), dtype=bool)
-            inside[tuple(slice(0, c) for c in W.coarse)] = True
-            val += l1 * float(np.abs(coef[~inside].astype(np.complex128)).sum())
+            val += l1 * wavelet_l1(q.to_host(), dims, W.coarse)
         objectives.append((k + 1, val))
         log.info("tv iter %d, objective %.9e", k + 1, val)
 
@@ -247,10 +282,11 @@ def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', le
 
 
 def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, width=3, fuse=True,
-                l1=0.0, wavelet='db2', levels=3, power_iters=15, step=None, tv=0.0, tv_sigma=None):
-    """ksp: (1, readout, views, C, 1, ...), mps: (X, Y, Z, C, 1), traj: (3, readout, views) in pixels -> image (X, Y, Z, 1, ...)
-    tv > 0: total-variation regularised by the primal-dual iteration (`tv_solve`; with l1 > 0 the wavelet term as well);
-    l1 > 0: L1-wavelet regularised by FISTA (`fista_solve`); else CG on the normal equations"""
+                l1=0.0, wavelet='db2', levels=3, power_iters=15, step=None, tv=0.0, tv_sigma=None, tv_time=0.0):
+    """ksp: (1, readout, views, C, 1, ..., T), mps: (X, Y, Z, C, 1), traj: (3, readout, views[, 1, ..., T]) in pixels -> image
+    (X, Y, Z, 1, ..., T).  T > 1 time frames: the block-diagonal problem of the module docstring, one A_t per frame.
+    tv > 0 (or, with T > 1, tv_time > 0): total-variation regularised by the primal-dual iteration (`tv_solve`; with l1 > 0 the
+    wavelet term as well); l1 > 0: L1-wavelet regularised by FISTA (`fista_solve`); else CG on the normal equations"""
     from indigo_amd.transforms import FuseZpadFFT, Optimize, sense_recipe
     from indigo_amd.transforms import reserve_for
     ksp = np.asarray(ksp, dtype=np.complex64)
@@ -263,32 +299,64 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
     for i in range(3):                                   # trajectory in units of the field of view (pics.py:69-72)
         traj[i] /= mps.shape[i]
     C = ksp.shape[dim.COIL]
-    assert (ksp.shape[dim.TIME] if ksp.ndim > dim.TIME else 1) == 1, "No support for multiple timepoints."
+    T = ksp.shape[dim.TIME] if ksp.ndim > dim.TIME else 1
     assert (mps.shape[dim.MAPS] if mps.ndim > dim.MAPS else 1) == 1, "No support for multiple maps."
-    trj3 = traj.reshape(traj.shape[:3])
-    F1 = B.NUFFT(ksp_nc_dims[:3], mps.shape[:3], trj3, width=width, oversamp=(osf, osf, osf), dtype=ksp.dtype)
-    F = B.KronI(C, F1)
-    S = B.VStack([B.Diag(mps[:, :, :, c].reshape(mps.shape[:3] + (1,))) for c in range(C)], name='maps')
-    A = F * S
-    A._name = 'SENSE1'
+    assert mps.ndim <= dim.TIME or mps.shape[dim.TIME] == 1, "The maps carry no TIME axis: one set for all frames."
+    T_traj = traj.shape[dim.TIME] if traj.ndim > dim.TIME else 1
+    assert T_traj in (1, T), "traj has %d time frames, data has %d" % (T_traj, T)
+    assert int(np.prod(ksp.shape[4:])) == T and int(np.prod(traj.shape[3:])) == T_traj, "Only COIL and TIME may be longer than 1."
     recipe = sense_recipe(level)
     if fuse and level >= 3:
         recipe = recipe + [FuseZpadFFT]
-    A = Optimize(recipe).visit(A)
-    AHA = (A.H * A) + lamda * B.Eye(A.shape[1])
-    AHA._name = 'SENSE'
-    reserve_for(AHA, 1, slack_products=6)
+
+    def frame_operators(trj3):
+        """A_t and A_t^H A_t + lamda I of one trajectory"""
+        F1 = B.NUFFT(ksp_nc_dims[:3], mps.shape[:3], trj3, width=width, oversamp=(osf, osf, osf), dtype=ksp.dtype)
+        F = B.KronI(C, F1)
+        S = B.VStack([B.Diag(mps[:, :, :, c].reshape(mps.shape[:3] + (1,))) for c in range(C)], name='maps')
+        A = F * S
+        A._name = 'SENSE1'
+        A = Optimize(recipe).visit(A)
+        AHA = (A.H * A) + lamda * B.Eye(A.shape[1])
+        AHA._name = 'SENSE'
+        return A, AHA
+
+    if T == 1:
+        A, AHA = frame_operators(traj.reshape(traj.shape[:3]))
+        reserve_for(AHA, 1, slack_products=6)
+    else:
+        # frames with equal trajectories share one tree: its matrices are built and uploaded once, and BlockDiag evaluates the
+        # same child on each of those frames' rows in turn
+        trjs = traj.reshape(traj.shape[:3] + (T_traj,))
+        distinct, trees, which = [], [], []
+        for t in range(T):
+            trj3 = trjs[..., t if T_traj > 1 else 0]
+            k = next((k for k, seen in enumerate(distinct) if np.array_equal(seen, trj3)), None)
+            if k is None:
+                k = len(distinct)
+                distinct.append(trj3)
+                trees.append(frame_operators(trj3))
+            which.append(k)
+        log.info("frames %d, distinct trajectories %d", T, len(distinct))
+        A = B.BlockDiag([trees[k][0] for k in which], name='SENSE1 frames')
+        AHA = B.BlockDiag([trees[k][1] for k in which], name='SENSE frames')
+        # the children run one after the other on the same arena: the scratch of the most demanding one, once
+        from indigo_amd.analyses import ScratchUsage
+        reserve_for(max((tree[1] for tree in trees), key=lambda node: ScratchUsage().measure(node, 1)), 1, slack_products=6)
     log.info("tree:\n%s", AHA.dump())
     log.info('using %d MB of device memory', (AHA.memusage() + 4 * AHA.shape[1] * ksp.dtype.itemsize) / 1e6)
     y = np.asfortranarray(ksp.reshape((-1, 1), order='F'))
     AHy = A.H * y
     scale = abs(AHy).max()
     AHy /= scale
-    if tv > 0 or l1 > 0:
+    if tv_time > 0 and T == 1:
+        log.info("--tv-time %g has no effect on a scan with one time frame", tv_time)
+        tv_time = 0.0
+    if tv > 0 or tv_time > 0 or l1 > 0:
         ynorm2 = float(np.vdot(y, y).real) / float(scale) ** 2          # the data term of the same normalised problem
-    if tv > 0:
+    if tv > 0 or tv_time > 0:
         x, _ = tv_solve(B, AHA, AHy, mps.shape[:3], iters, tv, sigma=tv_sigma, l1=l1, wavelet=wavelet, levels=levels,
-                        power_iters=power_iters, step=step, ynorm2=ynorm2)
+                        power_iters=power_iters, step=step, ynorm2=ynorm2, frames=T, mu_t=tv_time)
         return x.reshape(img_dims, order='F')
     if l1 > 0:
         x, _ = fista_solve(B, AHA, AHy, mps.shape[:3], iters, l1, wavelet=wavelet, levels=levels, power_iters=power_iters,
@@ -314,7 +382,7 @@ def main(argv=None, backend=None):
     trj = traj[tuple(slice(0, min(n, c)) for n, c in zip(traj.shape, crops[-traj.ndim:]))].T
     img = reconstruct(backend, ksp, mps, trj, iters=args.i, lamda=args.lamda, level=args.recipe, osf=args.osf,
                       width=args.width, fuse=not args.no_fuse, l1=args.l1, wavelet=args.wavelet, levels=args.levels,
-                      power_iters=args.power_iters, step=args.step, tv=args.tv, tv_sigma=args.tv_sigma)
+                      power_iters=args.power_iters, step=args.step, tv=args.tv, tv_sigma=args.tv_sigma, tv_time=args.tv_time)
     write(img.T)
     log.info("reconstruction complete")
     return img
