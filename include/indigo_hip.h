@@ -228,6 +228,22 @@ int  ig_grad4h_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t nt, 
  * of its own.  mu, mu_t >= 0 (0 gives exact zeros in that part); u must overlap neither xn nor xo (xn may be xo).             */
 int  ig_tv4_dual_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t nt, const void* xn, int64_t ldxn,
                      const void* xo, int64_t ldxo, float sigma, float mu, float mu_t, void* u, int64_t ldu);
+/* Block-wise singular-value thresholding and nuclear norms of the N x nt frame panel x: the proximal map and the value of the
+ * locally low-rank penalty (Backend.llr_threshold / llr_norm, pics --llr).  No reference counterpart.  The block
+ * sides b_a >= 1 are clamped to n_a, the shift is 0 <= s_a < b_a (of the clamped side).  Voxel i has the shifted coordinates
+ * j_a = (i_a + s_a) mod n_a and belongs to block (j_0 / b_0, j_1 / b_1, j_2 / b_2): the blocks tile the shifted volume, the last
+ * one of an axis is shorter when b_a does not divide n_a, and with a shift a block wraps around in i.  nb = prod ceil(n_a / b_a)
+ * blocks, numbered F-order.  M_b is the (voxels of block b) x nt matrix of x, sigma_k its singular values, V its right singular
+ * vectors (from the eigen-decomposition of M_b^H M_b, accumulated and solved in float64):
+ * ig_llr_svt_c64:  M_b <- M_b V diag(sigma_k > tau ? 1 - tau / sigma_k : 0) V^H in place, tau >= 0; tau >= every sigma_k gives
+ *                  exact zeros.  16 bytes per voxel and frame.
+ * ig_llr_nuc_c64:  nuc[b] = sum_k sigma_k  (nb floats; nuc overlapping x is IG_ERR_ARG).  8 bytes per voxel and frame.
+ * ldx >= N in elements; rows between the columns are never touched.  nt <= 32 and (clamped) blocks of at most 1024 voxels,
+ * else IG_ERR_UNSUPPORTED.                                                                                                    */
+int  ig_llr_svt_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t nt, int64_t b0, int64_t b1, int64_t b2,
+                    int64_t s0, int64_t s1, int64_t s2, float tau, void* x, int64_t ldx);
+int  ig_llr_nuc_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t nt, int64_t b0, int64_t b1, int64_t b2,
+                    int64_t s0, int64_t s1, int64_t s2, const void* x, int64_t ldx, float* nuc);
 
 /* ------------------------------------------------------------------------
  * CSR x dense-panel SpMM.  Replaces Backend.ccsrmm

@@ -720,6 +720,49 @@ class Backend(object):
             t[:, :, :, 3:] *= np.where(rt <= float(mu_t), 1.0, float(mu_t) / rt)
         u.copy_from(np.asfortranarray(t.astype(_C64).reshape(u.shape, order='F')))
 
+    @staticmethod
+    def _llr_block_ids(dims, block, shift):
+        """(block number of every voxel as an F-ordered (N,) array, nb, the clamped block) of the locally low-rank partition:
+        voxel i has the shifted coordinates j_a = (i_a + s_a) mod n_a and belongs to block (j_0 // b_0, j_1 // b_1, j_2 // b_2),
+        the blocks numbered F-order"""
+        dims = tuple(int(n) for n in dims)
+        block = tuple(min(int(b), n) for b, n in zip(block, dims))
+        shift = tuple(int(s) for s in shift)
+        assert len(dims) == 3 and all(b >= 1 for b in block) and all(0 <= s < b for s, b in zip(shift, block)), (dims, block, shift)
+        nbs = [-(-n // b) for n, b in zip(dims, block)]
+        per_axis = [((np.arange(n) + s) % n) // b for n, b, s in zip(dims, block, shift)]
+        ids = per_axis[0][:, None, None] + nbs[0] * (per_axis[1][None, :, None] + nbs[1] * per_axis[2][None, None, :])
+        return ids.reshape(-1, order='F'), int(np.prod(nbs)), block
+
+    def llr_threshold(self, x, tau, dims, frames, block, shift=(0, 0, 0)):
+        """Block-wise singular-value thresholding in place: the proximal map of tau * sum_b ||M_b(x)||_*, the locally low-rank
+        penalty.  x is the N x T panel of T = `frames` time frames of an F-ordered `dims` volume, or the same
+        as an (N T, 1) vector.  `block` sides are clamped to `dims`, 0 <= shift_a < block_a; the blocks tile the volume shifted
+        by `shift` (`_llr_block_ids`), M_b is the (voxels of block b) x T matrix of x, and M_b <- U max(S - tau, 0) V^H.
+        Host form in float64 through to_host / copy_from; device backends override it."""
+        n, T = int(np.prod(dims)), int(frames)
+        assert T >= 1 and x.size == n * T and tau >= 0, (x.shape, dims, frames, tau)
+        ids, nb, _ = self._llr_block_ids(dims, block, shift)
+        v = x.to_host().reshape((n, T), order='F').astype(np.complex128)
+        order = np.argsort(ids, kind='stable')
+        bounds = np.searchsorted(ids[order], np.arange(nb + 1))
+        for b in range(nb):
+            rows = order[bounds[b]:bounds[b + 1]]
+            U, S, Vh = np.linalg.svd(v[rows], full_matrices=False)
+            v[rows] = (U * np.maximum(S - float(tau), 0.0)) @ Vh
+        x.copy_from(np.asfortranarray(v.astype(_C64).reshape(x.shape, order='F')))
+
+    def llr_norm(self, x, dims, frames, block, shift=(0, 0, 0)):
+        """sum_b ||M_b(x)||_*, the sum of the singular values of every block's matrix (layouts and blocks as in `llr_threshold`),
+        as a float.  Host form in float64; device backends override it."""
+        n, T = int(np.prod(dims)), int(frames)
+        assert T >= 1 and x.size == n * T, (x.shape, dims, frames)
+        ids, nb, _ = self._llr_block_ids(dims, block, shift)
+        v = x.to_host().reshape((n, T), order='F').astype(np.complex128)
+        order = np.argsort(ids, kind='stable')
+        bounds = np.searchsorted(ids[order], np.arange(nb + 1))
+        return float(sum(np.linalg.svd(v[order[bounds[b]:bounds[b + 1]]], compute_uv=False).sum() for b in range(nb)))
+
     def supports_padded_fft(self, grid, ncoils=None):
         """whether `fft_padded` / `ifft_cropped[_sum]` exist for this oversampled grid (and, if given, this many coils)"""
         return False

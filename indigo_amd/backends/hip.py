@@ -873,6 +873,33 @@ class HipBackend(Backend):
         self._check(self._L.ig_tv4_dual_c64(self._ctx, n0, n1, n2, T, np_, ldn, op_, ldo, ctypes.c_float(float(sigma)),
                                             ctypes.c_float(float(mu)), ctypes.c_float(float(mu_t)), up, ldu), "ig_tv4_dual_c64")
 
+    def _llr_args(self, x, dims, frames, block, shift):
+        """the leading arguments of ig_llr_svt_c64 / ig_llr_nuc_c64, the panel pointer and its leading dimension, and nb"""
+        assert x.dtype == _C64, "only complex64 is supported"
+        dims = tuple(int(n) for n in dims)
+        T = int(frames)
+        xp, ldx = self._frame_panel(x, int(np.prod(dims)), T)
+        block = tuple(int(b) for b in block)
+        nb = int(np.prod([-(-n // max(1, min(b, n))) for n, b in zip(dims, block)]))
+        return dims + (T,) + block + tuple(int(s) for s in shift), xp, ldx, nb
+
+    def llr_threshold(self, x, tau, dims, frames, block, shift=(0, 0, 0)):
+        """Backend.llr_threshold on the device (ig_llr_svt_c64), in place: the frames are the columns of a panel with its
+        leading dimension, or stacked in one column"""
+        head, xp, ldx, _ = self._llr_args(x, dims, frames, block, shift)
+        self._check(self._L.ig_llr_svt_c64(self._ctx, *head, ctypes.c_float(float(tau)), xp, ldx), "ig_llr_svt_c64")
+
+    def llr_norm(self, x, dims, frames, block, shift=(0, 0, 0)):
+        """Backend.llr_norm on the device (ig_llr_nuc_c64): the blocks' nuclear norms as floats, summed on the host in float64"""
+        return float(self.llr_block_norms(x, dims, frames, block, shift).astype(np.float64).sum())
+
+    def llr_block_norms(self, x, dims, frames, block, shift=(0, 0, 0)):
+        """the nuclear norm of every block's matrix (ig_llr_nuc_c64): nb float32 on the host, blocks numbered F-order"""
+        head, xp, ldx, nb = self._llr_args(x, dims, frames, block, shift)
+        nuc = self.zero_array((max(nb, 1), 1), np.dtype('float32'), name='llr.nuc')
+        self._check(self._L.ig_llr_nuc_c64(self._ctx, *head, xp, ldx, ctypes.c_void_p(nuc._arr)), "ig_llr_nuc_c64")
+        return nuc.to_host().ravel()[:nb]
+
     def fftn(self, y, x):
         self._fft(y, x, -1)
 

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""Parallel-imaging reconstruction driver: non-Cartesian SENSE by conjugate gradients, L1-wavelet FISTA or total-variation primal-dual.
+"""Parallel-imaging reconstruction driver: non-Cartesian SENSE by conjugate gradients, L1-wavelet or locally low-rank FISTA, or
+total-variation primal-dual.
 
     python -m indigo_amd.pics [-i ITER] [--lamda L] [-O LEVEL] [--crop "COIL:2,TIME:1"] [--no-fuse] scan.h5 | scan.npz
     python -m indigo_amd.pics --l1 LAMBDA [--wavelet db2] [--levels 3] [--step S | --power-iters 15] ... scan.npz
     python -m indigo_amd.pics --tv MU [--tv-sigma S] [--l1 LAMBDA ...] [--step S | --power-iters 15] ... scan.npz
     python -m indigo_amd.pics --tv-time MU_T [--tv MU] [--l1 LAMBDA ...] ... frames.npz         (a scan with several time frames)
+    python -m indigo_amd.pics --llr LAMBDA [--llr-block 8] [--llr-shifts [--llr-seed 0]] [--tv MU] [--tv-time MU_T] ... frames.npz
 
 The counterpart of the reference's driver script (examples/pics.py:20-95 arguments, data layout and tree
 construction, :179-233 recipe, normal equations, CG, output): reads `data` (k-space), `maps` (coil sensitivities)
@@ -42,6 +44,20 @@ the term that couples the frames: `tv_solve` then uses operators.GradientT, a du
 `Backend.tv4_dual_step`, whose temporal component has its own constraint |u_3| <= MU_T.  The result keeps
 the TIME axis: (X, Y, Z, 1, ..., T).
 
+Locally low rank.  `--llr LAMBDA > 0` (`bart pics -R L:7:7:LAMBDA -b 8`) adds
+
+    LAMBDA sum_b ||M_b(x)||_*                                              (the nuclear norm: the sum of the singular values)
+
+where the blocks b of `--llr-block B` voxels a side (clamped to the volume; the last block of an axis is shorter) tile the
+volume and M_b is the (voxels of block b) x T matrix of the frames' values there.  Its proximal map is block-wise
+singular-value thresholding, `Backend.llr_threshold`, which takes the prox slot of the solver: `--llr` alone runs
+`Backend.fista` exactly as `--l1` does, with `--tv` and / or `--tv-time` it is the prox of `tv_solve` where the wavelet prox
+goes otherwise.  `--llr` with `--l1` is rejected: two non-smooth terms in one slot are not a prox.  Without `--llr-shifts` the
+partition is the one at shift (0, 0, 0) and the iteration is a true proximal method on the objective above.  With it a fresh
+shift is drawn before every prox call, uniformly in [0, side) per axis from numpy.random.default_rng(--llr-seed) on the host
+(every backend sees the same sequence; this is what bart does); the logged objective is that of shift 0 in both cases.  On
+one frame every block has rank one and the term shrinks the blocks' 2-norms.
+
 Containers: HDF5 (`.h5`, the reference's format; needs h5py, which this image does not ship) or NumPy `.npz` with
 the same three arrays in the same orientation; the result goes back into the HDF5 file as dataset `rec`, or next to
 an `.npz` input as `<name>.rec.npy`.
@@ -66,7 +82,7 @@ class dim:
 
 
 def parse(argv):
-    ap = argparse.ArgumentParser(prog="indigo_amd.pics", description="Parallel Imaging and Compressed Sensing (non-Cartesian SENSE: CG, L1-wavelet FISTA, or total-variation primal-dual).")
+    ap = argparse.ArgumentParser(prog="indigo_amd.pics", description="Parallel Imaging and Compressed Sensing (non-Cartesian SENSE: CG, L1-wavelet or locally-low-rank FISTA, or total-variation primal-dual).")
     ap.add_argument('-i', type=int, default=20, help='number of CG iterations')
     ap.add_argument('--backend', type=str, default='hip', choices=['hip'])
     ap.add_argument('--device', type=int, default=0)
@@ -85,8 +101,17 @@ def parse(argv):
     ap.add_argument('--tv', type=float, default=0, help='total-variation weight; > 0 solves by the primal-dual iteration (0: off)')
     ap.add_argument('--tv-sigma', type=float, default=None, help='dual step of --tv (default L / 24, with several time frames L / 32; L = 0.9 / the primal step)')
     ap.add_argument('--tv-time', type=float, default=0, help='weight of the total variation between neighbouring time frames (0: off; no effect on one frame)')
+    ap.add_argument('--llr', type=float, default=0, help='locally-low-rank weight; > 0 adds the blocks\' nuclear norms, by FISTA or as the prox of --tv / --tv-time (0: off)')
+    ap.add_argument('--llr-block', type=int, default=8, help='block side of --llr along all three axes (clamped to the volume)')
+    ap.add_argument('--llr-shifts', action='store_true', help='draw a fresh block shift before every prox call of --llr')
+    ap.add_argument('--llr-seed', type=int, default=0, help='seed of --llr-shifts')
     ap.add_argument('data', nargs='?', default="scan.h5", help='k-space data: HDF5 (data/maps/traj) or .npz')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.llr > 0 and args.l1 > 0:
+        ap.error("--llr and --l1 cannot be combined: two non-smooth terms in one prox slot are not a prox")
+    if args.llr_block < 1:
+        ap.error("--llr-block must be at least 1")
+    return args
 
 
 def load(path):
@@ -158,20 +183,64 @@ def wavelet_l1(coef, dims, coarse):
     return float(np.abs(coef[~inside].astype(np.complex128)).sum())
 
 
-def fista_solve(B, AHA, AHy, dims, iters, l1, wavelet='db2', levels=3, power_iters=15, step=None, ynorm2=0.0):
-    """min_x 1/2 x^H AHA x - Re(x^H AHy) + ynorm2 / 2 + l1 ||W x||_1 (W's coarse band excluded) by Backend.fista from x = 0;
-    with AHA = A^H A + lamda I and AHy = A^H y that is 1/2 ||A x - y||^2 + lamda/2 ||x||^2 + l1 ||W x||_1 for ynorm2 = ||y||^2.
+class ProxTerm:
+    """a non-smooth term g of the objective, as the solvers take it: proxg(v, alpha) replaces v by prox_{alpha g}(v) in place,
+    value(x) is g(x) as a float, text describes it in the log"""
+
+    def __init__(self, proxg, value, text):
+        self.proxg, self.value, self.text = proxg, value, text
+
+
+def wavelet_term(B, dims, l1, wavelet='db2', levels=3):
+    """l1 ||W x||_1 (W: operators.Wavelet on every frame, coarse band not penalised)"""
+    W = B.Wavelet(dims, wavelet=wavelet, levels=levels)
+    work = {}
+
+    def value(x):
+        if 'w' not in work:
+            work['w'] = B.zero_array(x.shape, np.dtype('complex64'), name='objective.w')
+        W.eval(work['w'], x)
+        return l1 * wavelet_l1(work['w'].to_host(), dims, W.coarse)
+    return ProxTerm(wavelet_prox(B, W, dims, l1), value,
+                    "%s wavelet, %d levels, coarse box %s of %s, l1 %g" % (wavelet, levels, W.coarse, tuple(dims), l1))
+
+
+def llr_term(B, dims, frames, lam, block=8, shifts=False, seed=0):
+    """lam sum_b ||M_b(x)||_*: the locally low-rank penalty on `frames` time frames with blocks of `block` voxels a side (clamped
+    to `dims`).  proxg is Backend.llr_threshold with the threshold alpha lam, at shift (0, 0, 0) or, with `shifts`, at a shift
+    drawn before every call, uniformly in [0, side) per axis from numpy.random.default_rng(seed) on the host.  value is that of
+    shift 0."""
+    dims = tuple(int(n) for n in dims)
+    T = int(frames)
+    sides = tuple(min(int(block), n) for n in dims)
+    rng = np.random.default_rng(seed) if shifts else None
+
+    def proxg(v, alpha):
+        shift = tuple(int(rng.integers(0, b)) for b in sides) if shifts else (0, 0, 0)
+        B.llr_threshold(v, alpha * lam, dims, T, sides, shift)
+
+    def value(x):
+        return lam * B.llr_norm(x, dims, T, sides)
+    return ProxTerm(proxg, value, "locally low rank, blocks %s of %s, %d frames, lambda %g, %s" % (
+        sides, dims, T, lam, "a random shift per prox call (seed %d)" % seed if shifts else "shift (0, 0, 0)"))
+
+
+def fista_solve(B, AHA, AHy, dims, iters, l1, wavelet='db2', levels=3, power_iters=15, step=None, ynorm2=0.0, term=None):
+    """min_x 1/2 x^H AHA x - Re(x^H AHy) + ynorm2 / 2 + g(x) by Backend.fista from x = 0, g = l1 ||W x||_1 (W's coarse band
+    excluded; `wavelet_term`) or the `term` given in its place (`llr_term`);
+    with AHA = A^H A + lamda I and AHy = A^H y that is 1/2 ||A x - y||^2 + lamda/2 ||x||^2 + g(x) for ynorm2 = ||y||^2.
     AHA of NT columns is T frames of the `dims` volume stacked: W and the threshold then act on every frame.
     Returns the image as a host (N, 1) array and the objectives logged: [(iteration, value)], every 10 iterations and the last."""
     c64 = np.dtype('complex64')
-    W = B.Wavelet(dims, wavelet=wavelet, levels=levels)
+    if term is None:
+        term = wavelet_term(B, dims, l1, wavelet, levels)
     if step is None:
         lam = power_iteration(B, AHA, power_iters)
         step = 0.9 / lam
         log.info("fista: largest eigenvalue of A^H A + lamda I %.6e (%d power iterations), step %.6e", lam, power_iters, step)
     else:
         log.info("fista: step %.6e (given)", step)
-    log.info("fista: %s wavelet, %d levels, coarse box %s of %s, l1 %g", wavelet, levels, W.coarse, tuple(dims), l1)
+    log.info("fista: %s", term.text)
     n = AHA.shape[1]
     b = B.copy_array(AHy, name='AHy')
 
@@ -179,7 +248,6 @@ def fista_solve(B, AHA, AHy, dims, iters, l1, wavelet='db2', levels=3, power_ite
         AHA.eval(g, z)
         B.axpby(1, g, -1, b)
 
-    proxg = wavelet_prox(B, W, dims, l1)
     objectives = []
     work = {}
 
@@ -188,25 +256,24 @@ def fista_solve(B, AHA, AHy, dims, iters, l1, wavelet='db2', levels=3, power_ite
             return
         if not work:
             work['q'] = B.zero_array((n, 1), c64, name='objective.q')
-            work['w'] = B.zero_array((n, 1), c64, name='objective.w')
-        q, w = work['q'], work['w']
+        q = work['q']
         AHA.eval(q, x)
-        W.eval(w, x)
-        val = 0.5 * B.dot(x, q) - B.dot(x, b) + 0.5 * ynorm2 + l1 * wavelet_l1(w.to_host(), dims, W.coarse)
+        val = 0.5 * B.dot(x, q) - B.dot(x, b) + 0.5 * ynorm2 + term.value(x)
         objectives.append((k + 1, val))
         log.info("fista iter %d, objective %.9e", k + 1, val)
 
     x = np.zeros((n, 1), dtype=c64, order='F')
-    B.fista(gradf, proxg, step, x, maxiter=iters, callback=objective)
+    B.fista(gradf, term.proxg, step, x, maxiter=iters, callback=objective)
     return x, objectives
 
 
 def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', levels=3, power_iters=15, step=None, ynorm2=0.0,
-             frames=1, mu_t=0.0):
+             frames=1, mu_t=0.0, term=None):
     """min_x 1/2 x^H AHA x - Re(x^H AHy) + ynorm2 / 2 + mu sum_i ||(D x)_i||_2 [+ l1 ||W x||_1] by Backend.primal_dual from x = 0,
     u = 0: with AHA = A^H A + lamda I and AHy = A^H y that is 1/2 ||A x - y||^2 + lamda/2 ||x||^2 + mu TV(x) [+ l1 ||W x||_1] for
     ynorm2 = ||y||^2.  D is operators.Gradient; the dual step is u <- proj_mu(u + sigma D(2 x_{k+1} - x_k)), the projection onto
-    the 2-norm ball of radius mu at every voxel (Backend.tv_dual_step); proxg is `wavelet_prox` when l1 > 0, else the identity.
+    the 2-norm ball of radius mu at every voxel (Backend.tv_dual_step); proxg is `wavelet_prox` when l1 > 0, that of `term`
+    (`llr_term`, whose value the objective then adds) when one is given, else the identity.
 
     Steps: L is the largest eigenvalue of AHA (`power_iteration`), or 0.9 / step when `step` is given; tau = 0.9 / L and
     sigma = L / 24 unless given.  With ||D||^2 <= 12:  1/tau - 12 sigma = L/0.9 - L/2 = 0.61 L >= L/2, the Condat-Vu condition.
@@ -232,11 +299,11 @@ def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', le
     log.info("tv: tau %.6e, sigma %.6e, mu %g, %s", tau, sigma, mu, tuple(dims))
     if T > 1:
         log.info("tv: %d frames, mu_t %g", T, mu_t)
-    W = proxg = None
+    assert term is None or not l1 > 0, "one prox slot: the wavelet term or `term`"
     if l1 > 0:
-        W = B.Wavelet(dims, wavelet=wavelet, levels=levels)
-        proxg = wavelet_prox(B, W, dims, l1)
-        log.info("tv: %s wavelet, %d levels, coarse box %s, l1 %g", wavelet, levels, W.coarse, l1)
+        term = wavelet_term(B, dims, l1, wavelet, levels)
+    if term is not None:
+        log.info("tv: %s", term.text)
     n = AHA.shape[1]
     b = B.copy_array(AHy, name='AHy')
     u = B.zero_array((comps * n, 1), c64, name='tv.u')
@@ -270,23 +337,24 @@ def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', le
         val = 0.5 * B.dot(x, q) - B.dot(x, b) + 0.5 * ynorm2 + mu * float(np.sqrt((np.abs(diffs[:, :3]) ** 2).sum(axis=1)).sum())
         if T > 1:
             val += mu_t * float(np.abs(diffs[:, 3]).sum())
-        if W is not None:
-            W.eval(q, x)
-            val += l1 * wavelet_l1(q.to_host(), dims, W.coarse)
+        if term is not None:
+            val += term.value(x)
         objectives.append((k + 1, val))
         log.info("tv iter %d, objective %.9e", k + 1, val)
 
     x = np.zeros((n, 1), dtype=c64, order='F')
-    B.primal_dual(gradf, proxg, KH, dual_step, tau, x, u, maxiter=iters, callback=objective)
+    B.primal_dual(gradf, term.proxg if term is not None else None, KH, dual_step, tau, x, u, maxiter=iters, callback=objective)
     return x, objectives
 
 
 def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, width=3, fuse=True,
-                l1=0.0, wavelet='db2', levels=3, power_iters=15, step=None, tv=0.0, tv_sigma=None, tv_time=0.0):
+                l1=0.0, wavelet='db2', levels=3, power_iters=15, step=None, tv=0.0, tv_sigma=None, tv_time=0.0,
+                llr=0.0, llr_block=8, llr_shifts=False, llr_seed=0):
     """ksp: (1, readout, views, C, 1, ..., T), mps: (X, Y, Z, C, 1), traj: (3, readout, views[, 1, ..., T]) in pixels -> image
     (X, Y, Z, 1, ..., T).  T > 1 time frames: the block-diagonal problem of the module docstring, one A_t per frame.
     tv > 0 (or, with T > 1, tv_time > 0): total-variation regularised by the primal-dual iteration (`tv_solve`; with l1 > 0 the
-    wavelet term as well); l1 > 0: L1-wavelet regularised by FISTA (`fista_solve`); else CG on the normal equations"""
+    wavelet term as well); l1 > 0: L1-wavelet regularised by FISTA (`fista_solve`); llr > 0: the locally low-rank term
+    (`llr_term`) in the prox slot of whichever of the two applies, in place of the wavelet term; else CG on the normal equations"""
     from indigo_amd.transforms import FuseZpadFFT, Optimize, sense_recipe
     from indigo_amd.transforms import reserve_for
     ksp = np.asarray(ksp, dtype=np.complex64)
@@ -352,15 +420,21 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
     if tv_time > 0 and T == 1:
         log.info("--tv-time %g has no effect on a scan with one time frame", tv_time)
         tv_time = 0.0
-    if tv > 0 or tv_time > 0 or l1 > 0:
+    term = None
+    if llr > 0:
+        assert not l1 > 0, "--llr and --l1 cannot be combined: two non-smooth terms in one prox slot are not a prox"
+        term = llr_term(B, mps.shape[:3], T, llr, block=llr_block, shifts=llr_shifts, seed=llr_seed)
+        if T == 1:
+            log.info("--llr on a scan with one time frame: every block has rank one, the term shrinks the blocks' 2-norms")
+    if tv > 0 or tv_time > 0 or l1 > 0 or llr > 0:
         ynorm2 = float(np.vdot(y, y).real) / float(scale) ** 2          # the data term of the same normalised problem
     if tv > 0 or tv_time > 0:
         x, _ = tv_solve(B, AHA, AHy, mps.shape[:3], iters, tv, sigma=tv_sigma, l1=l1, wavelet=wavelet, levels=levels,
-                        power_iters=power_iters, step=step, ynorm2=ynorm2, frames=T, mu_t=tv_time)
+                        power_iters=power_iters, step=step, ynorm2=ynorm2, frames=T, mu_t=tv_time, term=term)
         return x.reshape(img_dims, order='F')
-    if l1 > 0:
+    if l1 > 0 or llr > 0:
         x, _ = fista_solve(B, AHA, AHy, mps.shape[:3], iters, l1, wavelet=wavelet, levels=levels, power_iters=power_iters,
-                           step=step, ynorm2=ynorm2)
+                           step=step, ynorm2=ynorm2, term=term)
         return x.reshape(img_dims, order='F')
     x = np.zeros((AHA.shape[1], 1), dtype=ksp.dtype, order='F')
     hist = B.cg(AHA, AHy, x, maxiter=iters)
@@ -382,7 +456,8 @@ def main(argv=None, backend=None):
     trj = traj[tuple(slice(0, min(n, c)) for n, c in zip(traj.shape, crops[-traj.ndim:]))].T
     img = reconstruct(backend, ksp, mps, trj, iters=args.i, lamda=args.lamda, level=args.recipe, osf=args.osf,
                       width=args.width, fuse=not args.no_fuse, l1=args.l1, wavelet=args.wavelet, levels=args.levels,
-                      power_iters=args.power_iters, step=args.step, tv=args.tv, tv_sigma=args.tv_sigma, tv_time=args.tv_time)
+                      power_iters=args.power_iters, step=args.step, tv=args.tv, tv_sigma=args.tv_sigma, tv_time=args.tv_time,
+                      llr=args.llr, llr_block=args.llr_block, llr_shifts=args.llr_shifts, llr_seed=args.llr_seed)
     write(img.T)
     log.info("reconstruction complete")
     return img
