@@ -244,6 +244,17 @@ int  ig_llr_svt_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t nt,
                     int64_t s0, int64_t s1, int64_t s2, float tau, void* x, int64_t ldx);
 int  ig_llr_nuc_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t nt, int64_t b0, int64_t b1, int64_t b2,
                     int64_t s0, int64_t s1, int64_t s2, const void* x, int64_t ldx, float* nuc);
+/* The temporal-subspace operator Phi (x) I_n and its adjoint between nk coefficient images and nt time frames of n voxels
+ * (operators.FrameBasis, Backend.frame_basis, pics --basis).  No reference counterpart.  phi is a device array,
+ * nt x nk complex64, column-major with ldphi >= nt; x and y are column-major panels, ldx, ldy >= n in elements, and rows
+ * between the columns are never touched.
+ *   adjoint == 0:  y[i, t] = beta*y[i, t] + alpha * sum_k      phi[t, k]  * x[i, k]     (x: n x nk, y: n x nt)
+ *   adjoint != 0:  y[i, k] = beta*y[i, k] + alpha * sum_t conj(phi[t, k]) * x[i, t]     (x: n x nt, y: n x nk)
+ * beta == 0: y is not read.  A y that overlaps x or phi is IG_ERR_ARG, with nothing written.  1 <= nk <= 32, nt >= 1 and
+ * n >= 1, else IG_ERR_UNSUPPORTED.  One pass: 8 n (nk + nt) bytes, and 8 n (columns of y) more when beta != 0.              */
+int  ig_basis_c64(ig_ctx* ctx, int64_t n, int64_t nk, int64_t nt, const void* phi, int64_t ldphi, int adjoint,
+                  const void* x, int64_t ldx, float alpha_re, float alpha_im, float beta_re, float beta_im,
+                  void* y, int64_t ldy);
 
 /* ------------------------------------------------------------------------
  * CSR x dense-panel SpMM.  Replaces Backend.ccsrmm

@@ -86,7 +86,9 @@ PROTOTYPES = {
                                    c_float, c_void_p, c_int64]),
     "ig_llr_nuc_c64":     (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
                                    c_void_p, c_int64, c_void_p]),
-    "ig_ccsrmm_il":       (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64,
+    "ig_basis_c64":       (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64,
+                                   c_float, c_float, c_float, c_float, c_void_p, c_int64]),
+    "ig_ccsrmm_il":      (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64,
                                    c_float, c_float, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_float, c_float, c_void_p, c_int64]),
     "ig_ccsrmm_il_rw":    (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64,

@@ -483,6 +483,11 @@ class Backend(object):
         fourth component, shape (4NT, NT) (see operators.GradientT); .H is its adjoint"""
         return op.GradientT(self, dims, frames, **kwargs)
 
+    def FrameBasis(self, phi, n, **kwargs):
+        """Phi (x) I_n for the T x K temporal basis `phi` and images of `n` voxels, shape (nT, nK): K coefficient images stacked
+        coefficient-major in, T frames stacked frame-major out (see operators.FrameBasis); .H is its adjoint"""
+        return op.FrameBasis(self, phi, n, **kwargs)
+
     def Interp(self, N, coord, width, table, dtype=_C64, **kwargs):
         """gridding / interpolation matrix (npts x prod N) from a k-space trajectory"""
         assert len(N) == 3
@@ -762,6 +767,25 @@ class Backend(object):
         order = np.argsort(ids, kind='stable')
         bounds = np.searchsorted(ids[order], np.arange(nb + 1))
         return float(sum(np.linalg.svd(v[order[bounds[b]:bounds[b + 1]]], compute_uv=False).sum() for b in range(nb)))
+
+    def frame_basis(self, y, x, phi, n, adjoint=False, alpha=1, beta=0):
+        """y = beta*y + alpha * (Phi (x) I_n) x (adjoint: (Phi^H (x) I_n) x), the temporal-subspace operator between K coefficient
+        images and T time frames of `n` voxels.  phi is the T x K basis as a backend array.  Forward, x is the
+        n x K panel of the coefficient images, or the same as an (n K, 1) vector, image k in rows [kn, (k+1)n), and y the n x T
+        panel of the frames, or (n T, 1):  y[i, t] = sum_k phi[t, k] x[i, k].  Adjoint, x holds the frames and y the images:
+        y[i, k] = sum_t conj(phi[t, k]) x[i, t].  beta == 0: y is not read; y must not overlap x or phi.  Host form in float64
+        through to_host / copy_from; device backends override it."""
+        n = int(n)
+        p = phi.to_host().astype(np.complex128)
+        assert p.ndim == 2, p.shape
+        T, K = p.shape
+        cols_x, cols_y = (T, K) if adjoint else (K, T)
+        assert n >= 1 and x.size == n * cols_x and y.size == n * cols_y, (x.shape, y.shape, p.shape, n)
+        v = x.to_host().reshape((n, cols_x), order='F').astype(np.complex128)
+        out = (v @ p.conj() if adjoint else v @ p.T) * complex(alpha)
+        if beta != 0:
+            out = out + complex(beta) * y.to_host().reshape((n, cols_y), order='F')
+        y.copy_from(np.asfortranarray(out.astype(_C64).reshape(y.shape, order='F')))
 
     def supports_padded_fft(self, grid, ncoils=None):
         """whether `fft_padded` / `ifft_cropped[_sum]` exist for this oversampled grid (and, if given, this many coils)"""

@@ -900,6 +900,19 @@ class HipBackend(Backend):
         self._check(self._L.ig_llr_nuc_c64(self._ctx, *head, xp, ldx, ctypes.c_void_p(nuc._arr)), "ig_llr_nuc_c64")
         return nuc.to_host().ravel()[:nb]
 
+    def frame_basis(self, y, x, phi, n, adjoint=False, alpha=1, beta=0):
+        """Backend.frame_basis on the device (ig_basis_c64): the images and the frames are the columns of panels with their
+        leading dimensions, or stacked in one column"""
+        assert x.dtype == _C64 and y.dtype == _C64 and phi.dtype == _C64, "only complex64 is supported"
+        assert phi.ndim == 2, phi.shape
+        n, (T, K) = int(n), phi.shape
+        cols_x, cols_y = (T, K) if adjoint else (K, T)
+        (xp, ldx), (yp, ldy) = self._frame_panel(x, n, cols_x), self._frame_panel(y, n, cols_y)
+        ar, ai = _cplx(alpha)
+        br, bi = _cplx(beta)
+        self._check(self._L.ig_basis_c64(self._ctx, n, K, T, ctypes.c_void_p(phi._arr), phi._leading_dim, int(bool(adjoint)),
+                                         xp, ldx, ar, ai, br, bi, yp, ldy), "ig_basis_c64")
+
     def fftn(self, y, x):
         self._fft(y, x, -1)
 

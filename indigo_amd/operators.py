@@ -600,6 +600,47 @@ class GradientT(MatrixFreeOperator):
             self._backend.grad4(y[:, j:j + 1], x[:, j:j + 1], self._dims, self._frames, adjoint=not forward, alpha=alpha, beta=beta)
 
 
+class FrameBasis(MatrixFreeOperator):
+    """Phi (x) I_n: the temporal-subspace operator of a T x K complex64 basis `phi` on images of `n` voxels, shape (nT, nK).  The
+    input is K coefficient images stacked coefficient-major, image k in rows [kn, (k+1)n); the output is T frames stacked
+    frame-major, frame t = sum_k phi[t, k] * image k in rows [tn, (t+1)n), as `BlockDiag` and `GradientT` expect them.  .H is
+    the adjoint, image k = sum_t conj(phi[t, k]) * frame t.  Phi need not be orthonormal; K <= 32.  The basis goes to the
+    device once, on first evaluation.  The synthesis operator of pics --basis."""
+
+    def __init__(self, backend, phi, n, **kwargs):
+        try:
+            phi = np.require(np.asarray(phi), dtype=_C64, requirements='F')
+        except (TypeError, ValueError):
+            raise ValueError("FrameBasis: the basis does not convert to complex64")
+        if phi.ndim != 2:
+            raise ValueError("FrameBasis: the basis must be 2-D (frames x coefficients), got shape %s" % (phi.shape,))
+        T, K = phi.shape
+        if not 1 <= K <= 32 or T < 1:
+            raise ValueError("FrameBasis: a basis of %d frames x %d coefficients; between 1 and 32 coefficients and at least one "
+                             "frame are supported" % (T, K))
+        self._n = int(n)
+        if self._n < 1:
+            raise ValueError("FrameBasis: n must be positive, got %s" % (n,))
+        self._matrix = phi
+        self._matrix_d = None
+        kwargs.setdefault('name', 'basis')
+        super().__init__(backend, shape=(self._n * T, self._n * K), **kwargs)
+
+    def _eval(self, y, x, alpha=1, beta=0, forward=True, left=True):
+        if self._matrix_d is None:
+            self._matrix_d = self._backend.copy_array(self._matrix, name=self._name)
+        T, K = self._matrix.shape
+        trace = getattr(self._backend, 'trace', None)
+        if trace is not None:
+            # a single pass: every coefficient image and every frame moves once (8 B per voxel each); beta != 0 reads the output
+            trace.add('frame_basis', nbytes=8 * self._n * (K + T) * x.shape[1] + (0 if beta == 0 else y.nbytes), nflops=0,
+                      shape=x.shape, forward=forward, name=self._name)
+        if x.shape[1] == 1:
+            return self._backend.frame_basis(y, x, self._matrix_d, self._n, adjoint=not forward, alpha=alpha, beta=beta)
+        for j in range(x.shape[1]):             # the images become the columns of a panel inside: one product per column
+            self._backend.frame_basis(y[:, j:j + 1], x[:, j:j + 1], self._matrix_d, self._n, adjoint=not forward, alpha=alpha, beta=beta)
+
+
 class Eye(MatrixFreeOperator):
     def __init__(self, backend, n, **kwargs):
         super().__init__(backend, shape=(n, n), **kwargs)
@@ -759,7 +800,8 @@ class Kron(BinaryOperator):
         else:
             raise NotImplementedError(
                 "Kron with a non-identity left factor needs right-multiplication, which only the "
-                "reference's dense real-symmetric path provides; outside the SENSE hot path.")
+                "reference's dense real-symmetric path provides; outside the SENSE hot path.  For a temporal basis "
+                "Phi (x) I_n use FrameBasis(phi, n).")
 
 
 def _slice_rows(arr, start, stop):

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Parallel-imaging reconstruction driver: non-Cartesian SENSE by conjugate gradients, L1-wavelet or locally low-rank FISTA, or
-total-variation primal-dual.
+total-variation primal-dual; time frames one by one or in a temporal subspace.
 
     python -m indigo_amd.pics [-i ITER] [--lamda L] [-O LEVEL] [--crop "COIL:2,TIME:1"] [--no-fuse] scan.h5 | scan.npz
     python -m indigo_amd.pics --l1 LAMBDA [--wavelet db2] [--levels 3] [--step S | --power-iters 15] ... scan.npz
     python -m indigo_amd.pics --tv MU [--tv-sigma S] [--l1 LAMBDA ...] [--step S | --power-iters 15] ... scan.npz
     python -m indigo_amd.pics --tv-time MU_T [--tv MU] [--l1 LAMBDA ...] ... frames.npz         (a scan with several time frames)
     python -m indigo_amd.pics --llr LAMBDA [--llr-block 8] [--llr-shifts [--llr-seed 0]] [--tv MU] [--tv-time MU_T] ... frames.npz
+    python -m indigo_amd.pics --basis PHI.npy [--basis-rank K] [--l1 LAMBDA | --llr LAMBDA] [--tv MU] ... frames.npz
 
 The counterpart of the reference's driver script (examples/pics.py:20-95 arguments, data layout and tree
 construction, :179-233 recipe, normal equations, CG, output): reads `data` (k-space), `maps` (coil sensitivities)
@@ -58,6 +59,20 @@ shift is drawn before every prox call, uniformly in [0, side) per axis from nump
 (every backend sees the same sequence; this is what bart does); the logged objective is that of shift 0 in both cases.  On
 one frame every block has rank one and the term shrinks the blocks' 2-norms.
 
+Temporal subspace.  `--basis PHI.npy` (`bart pics -B`; PHI a real or complex T x K array, T the length of TIME, `--basis-rank K`
+keeps its first K columns, K <= 32) reconstructs the K coefficient images alpha_k of  x_t = sum_k PHI[t, k] alpha_k  in place of
+the T frames: scans of tens to hundreds of frames (multi-echo, T2 shuffling, fingerprinting) whose frames lie in a known
+low-dimensional subspace.  With A_t and their trees built as above, lamda left out of the frames,
+
+    A = BlockDiag(A_t) * FrameBasis(PHI, N),    A^H A + lamda I = FrameBasis^H * BlockDiag(A_t^H A_t) * FrameBasis + lamda I_{NK}
+
+(operators.FrameBasis = PHI (x) I_N, `Backend.frame_basis`).  PHI need not be orthonormal (||PHI^H PHI - I|| is
+logged; the step comes from the power iteration on this A^H A).  The unknown, the momentum, the TV dual and the LLR panel have K
+columns in place of T, and every regulariser acts on the coefficient images: CG solves the NK system, `--l1` thresholds every
+coefficient image, `--tv` is the spatial term on every coefficient image, `--llr` penalises the (block voxels) x K matrices, the
+T2-shuffling penalty.  `--tv-time` is rejected: differences between coefficient images are not differences in time.  The result
+is the coefficient images on the COEFF axis (dimension 6), (X, Y, Z, 1, 1, 1, K), with no TIME axis.
+
 Containers: HDF5 (`.h5`, the reference's format; needs h5py, which this image does not ship) or NumPy `.npz` with
 the same three arrays in the same orientation; the result goes back into the HDF5 file as dataset `rec`, or next to
 an `.npz` input as `<name>.rec.npy`.
@@ -78,7 +93,7 @@ log = logging.getLogger("pics")
 
 
 class dim:
-    READ, PHS1, PHS2, COIL, MAPS, TIME, NDIM = 0, 1, 2, 3, 4, 10, 20
+    READ, PHS1, PHS2, COIL, MAPS, COEFF, TIME, NDIM = 0, 1, 2, 3, 4, 6, 10, 20
 
 
 def parse(argv):
@@ -105,12 +120,21 @@ def parse(argv):
     ap.add_argument('--llr-block', type=int, default=8, help='block side of --llr along all three axes (clamped to the volume)')
     ap.add_argument('--llr-shifts', action='store_true', help='draw a fresh block shift before every prox call of --llr')
     ap.add_argument('--llr-seed', type=int, default=0, help='seed of --llr-shifts')
+    ap.add_argument('--basis', default=None, help='temporal basis, a .npy file with a T x K array: reconstruct the K coefficient images of the subspace')
+    ap.add_argument('--basis-rank', type=int, default=None, help='keep the first K columns of --basis')
     ap.add_argument('data', nargs='?', default="scan.h5", help='k-space data: HDF5 (data/maps/traj) or .npz')
     args = ap.parse_args(argv)
     if args.llr > 0 and args.l1 > 0:
         ap.error("--llr and --l1 cannot be combined: two non-smooth terms in one prox slot are not a prox")
     if args.llr_block < 1:
         ap.error("--llr-block must be at least 1")
+    if args.basis is not None and args.tv_time > 0:
+        ap.error("--tv-time cannot be combined with --basis: the unknowns are coefficient images, and differences between "
+                 "coefficients are not differences in time")
+    if args.basis_rank is not None and args.basis is None:
+        ap.error("--basis-rank needs --basis")
+    if args.basis_rank is not None and args.basis_rank < 1:
+        ap.error("--basis-rank must be at least 1")
     return args
 
 
@@ -144,6 +168,30 @@ def crop_limits(spec):
             crops[-(d + 1)] = int(size)
             log.info("cropping dim %d to length %d", d, int(size))
     return crops
+
+
+def subspace_basis(basis, frames, rank=None):
+    """the T x K complex64 basis of a `--basis` run: `basis` (real or complex, T x K') cut to its first `rank` columns, checked
+    against the scan's `frames` = T time frames and the 32 coefficient images that `Backend.frame_basis` serves"""
+    phi = np.asarray(basis)
+    if phi.ndim != 2:
+        raise ValueError("--basis: the basis must be a 2-D array (frames x coefficients), got shape %s" % (phi.shape,))
+    if frames < 2:
+        raise ValueError("--basis needs a scan with several time frames, this one has %d" % frames)
+    if phi.shape[0] != frames:
+        raise ValueError("--basis: the basis has %d rows, the scan has %d time frames" % (phi.shape[0], frames))
+    if rank is not None:
+        if rank < 1:
+            raise ValueError("--basis-rank must be at least 1, got %d" % rank)
+        if rank > phi.shape[1]:
+            raise ValueError("--basis-rank %d exceeds the %d columns of the basis" % (rank, phi.shape[1]))
+        phi = phi[:, :rank]
+    K = phi.shape[1]
+    if K < 1:
+        raise ValueError("--basis: the basis has no columns")
+    if K > 32:
+        raise ValueError("--basis: %d coefficients, at most 32 are supported (--basis-rank keeps the first K columns)" % K)
+    return np.asfortranarray(phi.astype(np.complex64))
 
 
 def power_iteration(B, AHA, iters, seed=0):
@@ -349,12 +397,14 @@ def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', le
 
 def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, width=3, fuse=True,
                 l1=0.0, wavelet='db2', levels=3, power_iters=15, step=None, tv=0.0, tv_sigma=None, tv_time=0.0,
-                llr=0.0, llr_block=8, llr_shifts=False, llr_seed=0):
+                llr=0.0, llr_block=8, llr_shifts=False, llr_seed=0, basis=None, basis_rank=None):
     """ksp: (1, readout, views, C, 1, ..., T), mps: (X, Y, Z, C, 1), traj: (3, readout, views[, 1, ..., T]) in pixels -> image
     (X, Y, Z, 1, ..., T).  T > 1 time frames: the block-diagonal problem of the module docstring, one A_t per frame.
     tv > 0 (or, with T > 1, tv_time > 0): total-variation regularised by the primal-dual iteration (`tv_solve`; with l1 > 0 the
     wavelet term as well); l1 > 0: L1-wavelet regularised by FISTA (`fista_solve`); llr > 0: the locally low-rank term
-    (`llr_term`) in the prox slot of whichever of the two applies, in place of the wavelet term; else CG on the normal equations"""
+    (`llr_term`) in the prox slot of whichever of the two applies, in place of the wavelet term; else CG on the normal equations.
+    basis: a T x K array (its first basis_rank columns): the temporal-subspace problem of the module docstring, whose unknowns and
+    result are the K coefficient images (X, Y, Z, 1, 1, 1, K); every regulariser then acts on those"""
     from indigo_amd.transforms import FuseZpadFFT, Optimize, sense_recipe
     from indigo_amd.transforms import reserve_for
     ksp = np.asarray(ksp, dtype=np.complex64)
@@ -373,19 +423,27 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
     T_traj = traj.shape[dim.TIME] if traj.ndim > dim.TIME else 1
     assert T_traj in (1, T), "traj has %d time frames, data has %d" % (T_traj, T)
     assert int(np.prod(ksp.shape[4:])) == T and int(np.prod(traj.shape[3:])) == T_traj, "Only COIL and TIME may be longer than 1."
+    phi = None
+    if basis is not None:
+        assert not tv_time > 0, "--tv-time cannot be combined with --basis: differences between coefficients are not differences in time"
+        phi = subspace_basis(basis, T, basis_rank)
+        K = phi.shape[1]
+        img_dims = mps.shape[:3] + (1,) * (dim.COEFF - 3) + (K,)
+        gram = phi.astype(np.complex128)
+        log.info("basis: %d frames, %d coefficients, ||Phi^H Phi - I|| %.3e", T, K, np.linalg.norm(gram.conj().T @ gram - np.eye(K)))
     recipe = sense_recipe(level)
     if fuse and level >= 3:
         recipe = recipe + [FuseZpadFFT]
 
     def frame_operators(trj3):
-        """A_t and A_t^H A_t + lamda I of one trajectory"""
+        """A_t and A_t^H A_t + lamda I of one trajectory (in a temporal subspace A_t^H A_t alone: lamda acts on the coefficients)"""
         F1 = B.NUFFT(ksp_nc_dims[:3], mps.shape[:3], trj3, width=width, oversamp=(osf, osf, osf), dtype=ksp.dtype)
         F = B.KronI(C, F1)
         S = B.VStack([B.Diag(mps[:, :, :, c].reshape(mps.shape[:3] + (1,))) for c in range(C)], name='maps')
         A = F * S
         A._name = 'SENSE1'
         A = Optimize(recipe).visit(A)
-        AHA = (A.H * A) + lamda * B.Eye(A.shape[1])
+        AHA = (A.H * A) + lamda * B.Eye(A.shape[1]) if phi is None else A.H * A
         AHA._name = 'SENSE'
         return A, AHA
 
@@ -410,7 +468,19 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
         AHA = B.BlockDiag([trees[k][1] for k in which], name='SENSE frames')
         # the children run one after the other on the same arena: the scratch of the most demanding one, once
         from indigo_amd.analyses import ScratchUsage
-        reserve_for(max((tree[1] for tree in trees), key=lambda node: ScratchUsage().measure(node, 1)), 1, slack_products=6)
+        worst = max((tree[1] for tree in trees), key=lambda node: ScratchUsage().measure(node, 1))
+        if phi is None:
+            reserve_for(worst, 1, slack_products=6)
+        else:
+            # x_t = sum_k Phi[t, k] alpha_k: the unknowns are the K coefficient images.  Below the frames' trees the three-factor
+            # product holds two panels of all T frames: the synthesised frames and what the frames' operators make of them
+            N = int(np.prod(mps.shape[:3]))
+            Phi = B.FrameBasis(phi, N, name='basis')
+            A = A * Phi
+            A._name = 'SENSE1 subspace'
+            AHA = Phi.H * AHA * Phi + lamda * B.Eye(N * K)
+            AHA._name = 'SENSE subspace'
+            reserve_for(worst, 1, slack_products=6, extra=2 * ((N * T + 31) // 32 * 32))
     log.info("tree:\n%s", AHA.dump())
     log.info('using %d MB of device memory', (AHA.memusage() + 4 * AHA.shape[1] * ksp.dtype.itemsize) / 1e6)
     y = np.asfortranarray(ksp.reshape((-1, 1), order='F'))
@@ -420,17 +490,18 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
     if tv_time > 0 and T == 1:
         log.info("--tv-time %g has no effect on a scan with one time frame", tv_time)
         tv_time = 0.0
+    cols = T if phi is None else K                       # the images of the unknown: the frames, or the coefficient images
     term = None
     if llr > 0:
         assert not l1 > 0, "--llr and --l1 cannot be combined: two non-smooth terms in one prox slot are not a prox"
-        term = llr_term(B, mps.shape[:3], T, llr, block=llr_block, shifts=llr_shifts, seed=llr_seed)
-        if T == 1:
+        term = llr_term(B, mps.shape[:3], cols, llr, block=llr_block, shifts=llr_shifts, seed=llr_seed)
+        if cols == 1:
             log.info("--llr on a scan with one time frame: every block has rank one, the term shrinks the blocks' 2-norms")
     if tv > 0 or tv_time > 0 or l1 > 0 or llr > 0:
         ynorm2 = float(np.vdot(y, y).real) / float(scale) ** 2          # the data term of the same normalised problem
     if tv > 0 or tv_time > 0:
         x, _ = tv_solve(B, AHA, AHy, mps.shape[:3], iters, tv, sigma=tv_sigma, l1=l1, wavelet=wavelet, levels=levels,
-                        power_iters=power_iters, step=step, ynorm2=ynorm2, frames=T, mu_t=tv_time, term=term)
+                        power_iters=power_iters, step=step, ynorm2=ynorm2, frames=cols, mu_t=tv_time, term=term)
         return x.reshape(img_dims, order='F')
     if l1 > 0 or llr > 0:
         x, _ = fista_solve(B, AHA, AHy, mps.shape[:3], iters, l1, wavelet=wavelet, levels=levels, power_iters=power_iters,
@@ -450,6 +521,7 @@ def main(argv=None, backend=None):
         backend = get_backend(args.backend, device_id=args.device)
     log.info("using backend: %s", type(backend).__name__)
     data, maps, traj, write = load(args.data)
+    basis = np.load(args.basis) if args.basis is not None else None
     crops = crop_limits(args.crop)
     ksp = data[tuple(slice(0, min(n, c)) for n, c in zip(data.shape, crops[-data.ndim:]))].T
     mps = maps[tuple(slice(0, min(n, c)) for n, c in zip(maps.shape, crops[-maps.ndim:]))].T
@@ -457,7 +529,8 @@ def main(argv=None, backend=None):
     img = reconstruct(backend, ksp, mps, trj, iters=args.i, lamda=args.lamda, level=args.recipe, osf=args.osf,
                       width=args.width, fuse=not args.no_fuse, l1=args.l1, wavelet=args.wavelet, levels=args.levels,
                       power_iters=args.power_iters, step=args.step, tv=args.tv, tv_sigma=args.tv_sigma, tv_time=args.tv_time,
-                      llr=args.llr, llr_block=args.llr_block, llr_shifts=args.llr_shifts, llr_seed=args.llr_seed)
+                      llr=args.llr, llr_block=args.llr_block, llr_shifts=args.llr_shifts, llr_seed=args.llr_seed,
+                      basis=basis, basis_rank=args.basis_rank)
     write(img.T)
     log.info("reconstruction complete")
     return img

@@ -68,12 +68,13 @@ class Optimize(Transform):
         return node
 
 
-def reserve_for(node, ncols=1, slack_products=2):
-    """Size and allocate `backend._scratch` for evaluating `node` (and `node.H * node`) on `ncols` columns."""
+def reserve_for(node, ncols=1, slack_products=2, extra=0):
+    """Size and allocate `backend._scratch` for evaluating `node` (and `node.H * node`) on `ncols` columns, with `extra` elements
+    for the temporaries of products that wrap `node`."""
     from indigo_amd.analyses import ScratchUsage
     elems = ScratchUsage().measure(node, ncols)
     # room for the extra Product levels of A^H*A (+ lamda*I): each adds one panel of A's rows or cols
-    extra = slack_products * ((max(node.shape) * ncols + 31) // 32 * 32)
+    extra = int(extra) + slack_products * ((max(node.shape) * ncols + 31) // 32 * 32)
     node._backend.reserve_scratch(elems + extra)
     return elems + extra
 
