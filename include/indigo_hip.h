@@ -255,6 +255,20 @@ int  ig_llr_nuc_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t nt,
 int  ig_basis_c64(ig_ctx* ctx, int64_t n, int64_t nk, int64_t nt, const void* phi, int64_t ldphi, int adjoint,
                   const void* x, int64_t ldx, float alpha_re, float alpha_im, float beta_re, float beta_im,
                   void* y, int64_t ldy);
+/* The K x K point-spread mixing pass of the Toeplitz normal operator (operators.ToeplitzNormal, Backend.psf_mix,
+ * pics --toeplitz).  No reference counterpart.
+ *   y[g, c, k] = sum_k' P[g][k, k'] * x[g, c, k']        g < n grid points, c < nc coils, k < nk
+ * x and y are device panels of nk columns, ldx and ldy in elements; inside a column element (g, c) sits at g*sg + c*sc:
+ * coil-major grids (sg = 1, sc >= n) or coil-interleaved ones (sc = 1, sg >= nc), g in the grid's memory order.  Elements of
+ * a column beyond those and rows of a padded leading dimension are never touched.  kern is a device array of nk^2 planes of
+ * n floats, P in the same grid order: the nk real diagonals of the Hermitian P, then re and im of every pair (k < k'), the
+ * pairs in row-major order of the upper triangle; P[k', k] = conj(P[k, k']).
+ * y == x with ldy == ldx is the in-place form; any other overlap of y with x or kern is IG_ERR_ARG, with nothing written.
+ * 1 <= nk <= 8, n >= 1 and nc >= 1, else IG_ERR_UNSUPPORTED.  The limit of 8 comes from memory, not registers: kern is
+ * 4 nk^2 n bytes, 8.6 GB at nk = 4 on a 512^3 grid, 34 GB at nk = 8, 137 GB at nk = 16.
+ * One pass: 16 n nc nk + 4 nk^2 n bytes.                                                                                  */
+int  ig_psf_mix_c64(ig_ctx* ctx, int64_t n, int64_t nc, int64_t nk, const float* kern, const void* x, int64_t ldx,
+                    void* y, int64_t ldy, int64_t sg, int64_t sc);
 
 /* ------------------------------------------------------------------------
  * CSR x dense-panel SpMM.  Replaces Backend.ccsrmm

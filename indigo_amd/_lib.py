@@ -88,6 +88,7 @@ PROTOTYPES = {
                                    c_void_p, c_int64, c_void_p]),
     "ig_basis_c64":       (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64,
                                    c_float, c_float, c_float, c_float, c_void_p, c_int64]),
+    "ig_psf_mix_c64":     (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64]),
     "ig_ccsrmm_il":      (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64,
                                    c_float, c_float, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_float, c_float, c_void_p, c_int64]),

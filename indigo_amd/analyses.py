@@ -49,6 +49,13 @@ class Memusage(Visitor):
             with self._push(self._live, self._round(node._mem_usage(self._ncols()))):
                 self._peak = max(self._peak, sum(self._live))
                 self.generic_visit(node)
+        elif isinstance(node, op.ToeplitzNormal):
+            # (its transforms are its own: K grid panels of one coil chunk and what that chunk's transform takes, and the kernel array)
+            if id(node) not in self._seen:
+                self._seen.add(id(node))
+                self._base += node.kernel_bytes()
+            with self._push(self._live, self._round(node._mem_usage(self._ncols()))):
+                self._peak = max(self._peak, sum(self._live))
         elif isinstance(node, op.Kron) and isinstance(node.left, op.Eye):
             with self._push(self._cols, node.left.shape[0]):
                 self.visit(node.right)

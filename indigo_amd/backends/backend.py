@@ -787,6 +787,52 @@ class Backend(object):
             out = out + complex(beta) * y.to_host().reshape((n, cols_y), order='F')
         y.copy_from(np.asfortranarray(out.astype(_C64).reshape(y.shape, order='F')))
 
+    @staticmethod
+    def psf_unpack(kern, n, K):
+        """the (n, K, K) complex128 Hermitian matrices of a `psf_mix` kernel array: K^2 planes of n floats, the K real diagonals,
+        then re and im of every pair (k < k'), the pairs in row-major order of the upper triangle"""
+        planes = np.asarray(kern, dtype=np.float64).reshape((K * K, n))
+        P = np.zeros((n, K, K), dtype=np.complex128)
+        for k in range(K):
+            P[:, k, k] = planes[k]
+        pair = 0
+        for a in range(K):
+            for b in range(a + 1, K):
+                P[:, a, b] = planes[K + 2 * pair] + 1j * planes[K + 2 * pair + 1]
+                P[:, b, a] = np.conj(P[:, a, b])
+                pair += 1
+        return P
+
+    def psf_mix(self, y, x, kern, n, ncoils, interleaved=False, width=None):
+        """y[g, c, k] = sum_k' P[g][k, k'] x[g, c, k'] over g < n grid points and c < ncoils coils: the K x K point-spread mixing
+        pass of the Toeplitz normal operator (operators.ToeplitzNormal).  x and y are panels of K columns, or
+        the same stacked in one column; a column holds the coils' grids one after the other (element (g, c) at g + n c), or,
+        `interleaved`, the `width` >= ncoils coil slots of a grid point side by side (element (g, c) at g width + c; slots
+        c >= ncoils are not touched), g in the grid's memory order.  kern is a float32 backend array of K^2 planes of n floats
+        in the same grid order (`psf_unpack`).  y may be x.  Host form in float64 through to_host / copy_from; device backends
+        override it."""
+        n, C = int(n), int(ncoils)
+        w = int(width) if (interleaved and width is not None) else C
+        K2 = kern.size // n
+        K = int(round(np.sqrt(K2)))
+        assert n >= 1 and C >= 1 and w >= C and K * K * n == kern.size, (kern.shape, n)
+        rows = n * w
+        assert x.size == rows * K and y.size == rows * K, (x.shape, y.shape, n, w, K)
+        P = self.psf_unpack(kern.to_host(), n, K)
+        shape = (w, n, K) if interleaved else (n, w, K)
+        v = x.to_host().reshape(shape, order='F').astype(np.complex128)
+        out = y.to_host().reshape(shape, order='F').copy()
+        if interleaved:
+            out[:C] = np.einsum('gab,cgb->cga', P, v[:C]).astype(_C64)
+        else:
+            out[:] = np.einsum('gab,gcb->gca', P, v).astype(_C64)
+        y.copy_from(np.asfortranarray(out.reshape(y.shape, order='F')))
+
+    def ToeplitzNormal(self, dims, maps, kern, K, **kwargs):
+        """A^H A of a (subspace) non-Cartesian SENSE problem as one Toeplitz operator on the grid of twice the image size, shape
+        (N K, N K) (see operators.ToeplitzNormal; the kernel comes from indigo_amd.toeplitz.psf_kernel); .H is itself"""
+        return op.ToeplitzNormal(self, dims, maps, kern, K, **kwargs)
+
     def supports_padded_fft(self, grid, ncoils=None):
         """whether `fft_padded` / `ifft_cropped[_sum]` exist for this oversampled grid (and, if given, this many coils)"""
         return False

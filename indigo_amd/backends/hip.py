@@ -913,6 +913,19 @@ class HipBackend(Backend):
         self._check(self._L.ig_basis_c64(self._ctx, n, K, T, ctypes.c_void_p(phi._arr), phi._leading_dim, int(bool(adjoint)),
                                          xp, ldx, ar, ai, br, bi, yp, ldy), "ig_basis_c64")
 
+    def psf_mix(self, y, x, kern, n, ncoils, interleaved=False, width=None):
+        """Backend.psf_mix on the device (ig_psf_mix_c64): the K images are the columns of panels with their leading
+        dimensions, or stacked in one column; y may be x"""
+        assert x.dtype == _C64 and y.dtype == _C64 and kern.dtype == np.dtype('float32'), "complex64 panels and a float32 kernel array"
+        n, C = int(n), int(ncoils)
+        w = int(width) if (interleaved and width is not None) else C
+        K = int(round(np.sqrt(kern.size // max(n, 1))))
+        assert K * K * n == kern.size and kern.contiguous and w >= C, (kern.shape, n, C, w)
+        rows = n * w
+        (xp, ldx), (yp, ldy) = self._frame_panel(x, rows, K), self._frame_panel(y, rows, K)
+        sg, sc = (w, 1) if interleaved else (1, n)
+        self._check(self._L.ig_psf_mix_c64(self._ctx, n, C, K, ctypes.c_void_p(kern._arr), xp, ldx, yp, ldy, sg, sc), "ig_psf_mix_c64")
+
     def fftn(self, y, x):
         self._fft(y, x, -1)
 

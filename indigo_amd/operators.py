@@ -641,6 +641,121 @@ class FrameBasis(MatrixFreeOperator):
             self._backend.frame_basis(y[:, j:j + 1], x[:, j:j + 1], self._matrix_d, self._n, adjoint=not forward, alpha=alpha, beta=beta)
 
 
+class ToeplitzNormal(MatrixFreeOperator):
+    """A^H A of a non-Cartesian SENSE problem -- in a temporal subspace of K coefficient images, or K = 1 for one frame -- as ONE
+    Toeplitz operator, shape (N K, N K):
+
+        (A^H A alpha)_k = sum_c S_c^H crop F^-1 ( sum_k' P_kk' . (F zpad S_c alpha_k') )
+
+    S_c the coil maps `maps` (dims + (C,)), F the plain FFT on the grid of twice the image size `dims`, P the K x K Hermitian
+    matrix of transformed point-spread functions at every grid point (indigo_amd.toeplitz.psf_kernel, all constants folded
+    in).  No gridding, no per-frame trees, no frame panels: per evaluation C K padded transforms each way and one streaming
+    pass (Backend.psf_mix).  The input and the output are K images stacked coefficient-major, as `FrameBasis` takes them.
+
+    `kern` is a host float32 array (K^2, 8N): the planes of `Backend.psf_unpack`, each flattened in the memory order `order` of
+    the grid: 'xyz' (F order) or 'xzy' (the order of ZpadFFT's layouts 1 and 2).  `memory_order(backend, dims)` tells which of
+    the two the operator runs in; a kernel in the other order is transposed on the host before it is uploaded, once, on the
+    first evaluation.  Where the backend has zero-pad-aware transforms for the grid (`supports_padded_fft`) the coils go through
+    `ZpadFFT` leaves in the chunks of `fused.plan_chunks`; else through the unfused composition Crop * UnscaledFFT * Zpad, `chunk`
+    coils at a time.  Scratch: K grid panels of one chunk, and what the chunk's transform takes.  Hermitian: .H is the
+    operator itself.  DESIGN.md §3.11."""
+
+    MAXK = 8          # the kernel array is 4 K^2 bytes per grid point: 8.6 GB at K = 4 on a 512^3 grid, 34 GB at K = 8, 137 GB at K = 16
+
+    @staticmethod
+    def memory_order(backend, dims):
+        return 'xzy' if backend.supports_padded_fft(tuple(2 * int(n) for n in dims)) else 'xyz'
+
+    def __init__(self, backend, dims, maps, kern, K, order='xyz', chunk=8, **kwargs):
+        from indigo_amd import fused
+        self._dims = tuple(int(n) for n in dims)
+        if len(self._dims) != 3 or min(self._dims) < 1:
+            raise ValueError("ToeplitzNormal: dims must be three positive lengths, got %s" % (dims,))
+        self._K = int(K)
+        if not 1 <= self._K <= self.MAXK:
+            raise ValueError("ToeplitzNormal: %d coefficient images, between 1 and %d are supported: the kernel array holds 4 K^2 bytes "
+                             "per grid point (34 GB at K = 8 on a 512^3 grid, 137 GB at K = 16)" % (self._K, self.MAXK))
+        self._grid = tuple(2 * n for n in self._dims)
+        N, P = int(np.prod(self._dims)), int(np.prod(self._grid))
+        maps = np.asarray(maps, dtype=_C64)
+        if maps.ndim == 3:
+            maps = maps.reshape(maps.shape + (1,))
+        if maps.ndim != 4 or maps.shape[:3] != self._dims:
+            raise ValueError("ToeplitzNormal: maps must be dims + (coils,), got shape %s for dims %s" % (maps.shape, self._dims))
+        C = self._C = int(maps.shape[3])
+        kern = np.asarray(kern, dtype=np.float32)
+        if kern.size != self._K ** 2 * P or order not in ('xyz', 'xzy'):
+            raise ValueError("ToeplitzNormal: a kernel of %d floats in order %r; K^2 = %d planes of the %s grid in 'xyz' or 'xzy' order "
+                             "are expected" % (kern.size, order, self._K ** 2, self._grid))
+        self._kern_h, self._kern_order, self._kern_d = kern.reshape((self._K ** 2, P)), order, None
+        self._order = self.memory_order(backend, self._dims)
+        self._parts = []                                 # (transform operator, real coils, coil slots, interleaved)
+        if self._order == 'xzy':
+            single_ok = getattr(backend, 'supports_single_coil_layout', lambda g: True)(self._grid)
+            tuning = getattr(backend, 'tuning', {})
+            for lo, hi, w in fused.plan_chunks(C, chunk, single_ok, tuning.get('chunk_cost'), tuning.get('chunk_pad', True)):
+                wts = fused.pad_coils(maps[..., lo:hi], w) if w > 1 else np.asfortranarray(maps[..., lo:hi])
+                Z = backend.ZpadFFT(self._grid, self._dims, wts, layout=2 if w > 1 else 1, name='fft*zpad*maps')
+                self._parts.append((Z, hi - lo, w, w > 1))
+        else:
+            for lo in range(0, C, int(chunk)):
+                hi = min(lo + int(chunk), C)
+                c = hi - lo
+                S = backend.VStack([backend.Diag(maps[:, :, :, i].reshape(self._dims + (1,))) for i in range(lo, hi)], name='maps')
+                F = backend.KronI(c, backend.UnscaledFFT(self._grid, name='fft')) * backend.KronI(c, backend.Zpad(self._grid, self._dims, name='zpad')) * S
+                self._parts.append((F, c, c, False))
+        kwargs.setdefault('name', 'toeplitz')
+        super().__init__(backend, shape=(N * self._K, N * self._K), **kwargs)
+
+    @property
+    def H(self):
+        return self
+
+    def kernel_bytes(self):
+        return self._K ** 2 * int(np.prod(self._grid)) * 4
+
+    def _kernel(self):
+        if self._kern_d is None:
+            k = self._kern_h
+            if self._kern_order != self._order:
+                g = self._grid
+                shape = (g[0], g[1], g[2]) if self._kern_order == 'xyz' else (g[0], g[2], g[1])
+                k = np.stack([p.reshape(shape, order='F').transpose(0, 2, 1).reshape(-1, order='F') for p in k])
+            self._kern_d = self._backend.copy_array(np.ascontiguousarray(k).reshape(-1), name=self._name + '.psf')
+            self._kern_h = None
+        return self._kern_d
+
+    def _mem_usage(self, ncols):
+        from indigo_amd.analyses import ScratchUsage
+        P, worst = int(np.prod(self._grid)), 0
+        for T, real, w, il in self._parts:
+            panel = (P * w * self._K + 31) // 32 * 32
+            worst = max(worst, (panel + ScratchUsage().measure(T, 1)) * 8)
+        return worst
+
+    def _eval(self, y, x, alpha=1, beta=0, forward=True, left=True):
+        B, K = self._backend, self._K
+        N, P = int(np.prod(self._dims)), int(np.prod(self._grid))
+        kern = self._kernel()
+        fused_path = self._order == 'xzy'
+        trace = getattr(B, 'trace', None)
+        for j in range(x.shape[1]):
+            xj = x if x.shape[1] == 1 else x[:, j:j + 1]
+            yj = y if y.shape[1] == 1 else y[:, j:j + 1]
+            for i, (T, real, w, il) in enumerate(self._parts):
+                with B.scratch(shape=(P * w, K)) as panel:
+                    cols = [panel[:, k:k + 1] for k in range(K)]
+                    for k in range(K):
+                        # (the unfused transforms take alpha == 1 only: there alpha rides on the maps of the way in)
+                        T.eval(cols[k], xj.dense_rows(k * N, (k + 1) * N), alpha=1 if fused_path else alpha, beta=0, forward=True)
+                    if trace is not None:
+                        trace.add('psf_mix', nbytes=16 * P * real * K + 4 * K * K * P, nflops=8 * P * real * K * K, shape=(P, real, K), name=self._name)
+                    B.psf_mix(panel, panel, kern, P, real, interleaved=il, width=w)
+                    for k in range(K):
+                        T.eval(yj.dense_rows(k * N, (k + 1) * N), cols[k], alpha=alpha if fused_path else 1,
+                               beta=beta if i == 0 else 1, forward=False)
+
+
 class Eye(MatrixFreeOperator):
     def __init__(self, backend, n, **kwargs):
         super().__init__(backend, shape=(n, n), **kwargs)

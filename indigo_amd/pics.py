@@ -8,6 +8,7 @@ total-variation primal-dual; time frames one by one or in a temporal subspace.
     python -m indigo_amd.pics --tv-time MU_T [--tv MU] [--l1 LAMBDA ...] ... frames.npz         (a scan with several time frames)
     python -m indigo_amd.pics --llr LAMBDA [--llr-block 8] [--llr-shifts [--llr-seed 0]] [--tv MU] [--tv-time MU_T] ... frames.npz
     python -m indigo_amd.pics --basis PHI.npy [--basis-rank K] [--l1 LAMBDA | --llr LAMBDA] [--tv MU] ... frames.npz
+    python -m indigo_amd.pics --toeplitz [--basis PHI.npy ...] ... scan.npz | frames.npz        (A^H A as one Toeplitz operator)
 
 The counterpart of the reference's driver script (examples/pics.py:20-95 arguments, data layout and tree
 construction, :179-233 recipe, normal equations, CG, output): reads `data` (k-space), `maps` (coil sensitivities)
@@ -73,6 +74,17 @@ coefficient image, `--tv` is the spatial term on every coefficient image, `--llr
 T2-shuffling penalty.  `--tv-time` is rejected: differences between coefficient images are not differences in time.  The result
 is the coefficient images on the COEFF axis (dimension 6), (X, Y, Z, 1, 1, 1, K), with no TIME axis.
 
+Toeplitz normal operator.  `--toeplitz` (bart's Toeplitz mode) replaces A^H A in every solver by `operators.ToeplitzNormal`:
+sum_c S_c^H crop F^-1 P F zpad S_c on the grid of twice the image size, S_c the maps alone, F a plain FFT, P the transformed
+point-spread functions (indigo_amd.toeplitz.psf_kernel: one adjoint NUFFT of ones onto the doubled image per distinct trajectory,
+with the run's `--width` and `--osf`).  With `--basis`, P is a K x K Hermitian matrix at every grid point,
+P_kk' = FFT(sum_t conj(PHI[t, k]) PHI[t, k'] q_t), and A^H A + lamda I = lamda I + ToeplitzNormal(K): the cost of an iteration
+depends on K, not on T, and no frame panel is held (K <= 8: the kernel array is 4 K^2 bytes per point of the doubled grid).
+Without a basis every distinct trajectory gets its own ToeplitzNormal(K = 1) under the frames' `BlockDiag`, or alone for one frame.
+A and A^H y stay the gridding operator, which is used once; CG, `--l1`, `--tv`, `--tv-time` and `--llr` and the power iteration
+run unchanged on the new A^H A.  The two forms of A^H A differ by the NUFFT's own approximation error (the gridding form carries
+it twice, the Toeplitz form once).  Without `--toeplitz` the driver runs the code it ran before.
+
 Containers: HDF5 (`.h5`, the reference's format; needs h5py, which this image does not ship) or NumPy `.npz` with
 the same three arrays in the same orientation; the result goes back into the HDF5 file as dataset `rec`, or next to
 an `.npz` input as `<name>.rec.npy`.
@@ -122,6 +134,7 @@ def parse(argv):
     ap.add_argument('--llr-seed', type=int, default=0, help='seed of --llr-shifts')
     ap.add_argument('--basis', default=None, help='temporal basis, a .npy file with a T x K array: reconstruct the K coefficient images of the subspace')
     ap.add_argument('--basis-rank', type=int, default=None, help='keep the first K columns of --basis')
+    ap.add_argument('--toeplitz', action='store_true', help='evaluate A^H A as one Toeplitz operator on the grid of twice the image size (with --basis: K x K point-spread functions, the cost no longer grows with the frames)')
     ap.add_argument('data', nargs='?', default="scan.h5", help='k-space data: HDF5 (data/maps/traj) or .npz')
     args = ap.parse_args(argv)
     if args.llr > 0 and args.l1 > 0:
@@ -135,6 +148,9 @@ def parse(argv):
         ap.error("--basis-rank needs --basis")
     if args.basis_rank is not None and args.basis_rank < 1:
         ap.error("--basis-rank must be at least 1")
+    if args.toeplitz and args.basis_rank is not None and args.basis_rank > 8:
+        ap.error("--toeplitz serves at most 8 coefficient images (--basis-rank %d): its kernel array holds 4 K^2 bytes per point "
+                 "of the doubled grid, 137 GB at K = 16 on a 512^3 grid" % args.basis_rank)
     return args
 
 
@@ -192,6 +208,37 @@ def subspace_basis(basis, frames, rank=None):
     if K > 32:
         raise ValueError("--basis: %d coefficients, at most 32 are supported (--basis-rank keeps the first K columns)" % K)
     return np.asfortranarray(phi.astype(np.complex64))
+
+
+def toeplitz_normal(B, mps, distinct, which, phi, lamda, width, osf, recipe=None):
+    """A^H A + lamda I of `reconstruct` in Toeplitz form, with the scratch arena reserved for it.  phi (T x K): one
+    `ToeplitzNormal` of K coefficient images; phi None: one `ToeplitzNormal` (K = 1) per distinct trajectory, each + lamda I, under a
+    `BlockDiag` over the frames `which`, or alone for one frame.  distinct: the trajectories (3, readout, views) in cycles per pixel;
+    recipe: the pass list of the run's own trees, for the set-up transform of `psf_kernel`."""
+    from indigo_amd.operators import ToeplitzNormal
+    from indigo_amd.toeplitz import psf_kernel
+    from indigo_amd.transforms import reserve_for
+    dims = tuple(int(n) for n in mps.shape[:3])
+    N = int(np.prod(dims))
+    maps = mps.reshape(dims + (-1,))
+    order = ToeplitzNormal.memory_order(B, dims)
+    if phi is not None:
+        K = phi.shape[1]
+        kern = psf_kernel(B, dims, distinct, which, phi, width, osf, order=order, recipe=recipe)
+        # (lamda I + T, not T + lamda I: a Sum evaluates its right child first, with the caller's beta, so T runs with beta = 0)
+        AHA = lamda * B.Eye(N * K) + B.ToeplitzNormal(dims, maps, kern, K, order=order, name='toeplitz subspace')
+        AHA._name = 'SENSE subspace (Toeplitz)'
+        reserve_for(AHA, 1, slack_products=6)
+        return AHA
+    ops = []
+    for k, trj3 in enumerate(distinct):
+        kern = psf_kernel(B, dims, [trj3], [0], None, width, osf, order=order, recipe=recipe)
+        ops.append(lamda * B.Eye(N) + B.ToeplitzNormal(dims, maps, kern, 1, order=order, name='toeplitz'))
+        ops[-1]._name = 'SENSE (Toeplitz)'
+    AHA = ops[0] if len(which) == 1 else B.BlockDiag([ops[k] for k in which], name='SENSE frames (Toeplitz)')
+    # (the children run one after the other on the same arena, and all have the same size)
+    reserve_for(ops[0], 1, slack_products=6)
+    return AHA
 
 
 def power_iteration(B, AHA, iters, seed=0):
@@ -397,14 +444,15 @@ def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', le
 
 def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, width=3, fuse=True,
                 l1=0.0, wavelet='db2', levels=3, power_iters=15, step=None, tv=0.0, tv_sigma=None, tv_time=0.0,
-                llr=0.0, llr_block=8, llr_shifts=False, llr_seed=0, basis=None, basis_rank=None):
+                llr=0.0, llr_block=8, llr_shifts=False, llr_seed=0, basis=None, basis_rank=None, toeplitz=False):
     """ksp: (1, readout, views, C, 1, ..., T), mps: (X, Y, Z, C, 1), traj: (3, readout, views[, 1, ..., T]) in pixels -> image
     (X, Y, Z, 1, ..., T).  T > 1 time frames: the block-diagonal problem of the module docstring, one A_t per frame.
     tv > 0 (or, with T > 1, tv_time > 0): total-variation regularised by the primal-dual iteration (`tv_solve`; with l1 > 0 the
     wavelet term as well); l1 > 0: L1-wavelet regularised by FISTA (`fista_solve`); llr > 0: the locally low-rank term
     (`llr_term`) in the prox slot of whichever of the two applies, in place of the wavelet term; else CG on the normal equations.
     basis: a T x K array (its first basis_rank columns): the temporal-subspace problem of the module docstring, whose unknowns and
-    result are the K coefficient images (X, Y, Z, 1, 1, 1, K); every regulariser then acts on those"""
+    result are the K coefficient images (X, Y, Z, 1, 1, 1, K); every regulariser then acts on those.
+    toeplitz: A^H A of every solver is `operators.ToeplitzNormal` (module docstring); A^H y still comes from the gridding operator"""
     from indigo_amd.transforms import FuseZpadFFT, Optimize, sense_recipe
     from indigo_amd.transforms import reserve_for
     ksp = np.asarray(ksp, dtype=np.complex64)
@@ -431,6 +479,9 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
         img_dims = mps.shape[:3] + (1,) * (dim.COEFF - 3) + (K,)
         gram = phi.astype(np.complex128)
         log.info("basis: %d frames, %d coefficients, ||Phi^H Phi - I|| %.3e", T, K, np.linalg.norm(gram.conj().T @ gram - np.eye(K)))
+        if toeplitz and K > 8:
+            raise ValueError("--toeplitz: %d coefficients, at most 8 are supported: the kernel array holds 4 K^2 bytes per point of the "
+                             "doubled grid, %.1f GB here (--basis-rank keeps the first K columns)" % (K, 32e-9 * K * K * int(np.prod(mps.shape[:3]))))
     recipe = sense_recipe(level)
     if fuse and level >= 3:
         recipe = recipe + [FuseZpadFFT]
@@ -448,7 +499,8 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
         return A, AHA
 
     if T == 1:
-        A, AHA = frame_operators(traj.reshape(traj.shape[:3]))
+        distinct, which = [traj.reshape(traj.shape[:3])], [0]
+        A, AHA = frame_operators(distinct[0])
         reserve_for(AHA, 1, slack_products=6)
     else:
         # frames with equal trajectories share one tree: its matrices are built and uploaded once, and BlockDiag evaluates the
@@ -487,6 +539,14 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
     AHy = A.H * y
     scale = abs(AHy).max()
     AHy /= scale
+    if toeplitz:
+        # the gridding operator has done its one job, the right-hand side: every solver below runs on the Toeplitz form of A^H A
+        del A, AHA
+        if T > 1:
+            del trees, worst
+        B._scratch = None
+        AHA = toeplitz_normal(B, mps, distinct, which, phi, lamda, width, osf, recipe=recipe)
+        log.info("tree:\n%s", AHA.dump())
     if tv_time > 0 and T == 1:
         log.info("--tv-time %g has no effect on a scan with one time frame", tv_time)
         tv_time = 0.0
@@ -530,7 +590,7 @@ def main(argv=None, backend=None):
                       width=args.width, fuse=not args.no_fuse, l1=args.l1, wavelet=args.wavelet, levels=args.levels,
                       power_iters=args.power_iters, step=args.step, tv=args.tv, tv_sigma=args.tv_sigma, tv_time=args.tv_time,
                       llr=args.llr, llr_block=args.llr_block, llr_shifts=args.llr_shifts, llr_seed=args.llr_seed,
-                      basis=basis, basis_rank=args.basis_rank)
+                      basis=basis, basis_rank=args.basis_rank, toeplitz=args.toeplitz)
     write(img.T)
     log.info("reconstruction complete")
     return img
