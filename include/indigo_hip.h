@@ -64,7 +64,10 @@ int  ig_device_name(ig_ctx* ctx, char* buf, size_t len);
 int  ig_mem_info(ig_ctx* ctx, size_t* free_bytes, size_t* total_bytes);
 /* Plan options, read when a plan is made.  "fft.kernels": 0 = every kernel (default), 1 = no register-resident A x B passes
  * (160 ... 640-point axes take the multi-stage LDS kernel), 2 = only the one-stage-per-launch generic kernel -- the
- * fallback kernels stay testable on sizes the fast ones would take.  Unknown names are an error.                          */
+ * fallback kernels stay testable on sizes the fast ones would take.  Unknown names are an error.
+ * "fft.zc_intermediate" (read by every zero-padded / cropped transform of the coil-interleaved layout, existing plans included):
+ * 1 = the array its y and z passes exchange is stored z-contiguous per kx tile (ig_fft_zc_offset), 0 = in the grid's order.
+ * Results are bit-identical either way; the workspace is the same.                                                        */
 int  ig_set_option(ig_ctx* ctx, const char* name, int64_t value);
 /* Device memory the library holds on its own for this context (the SpMM kernels' repacked-panel buffer, deferred-row lists,
  * reduction scratch, solver scalars): what Backend.mem_usage() adds to the arrays the caller allocated.                    */
@@ -655,6 +658,12 @@ int  ig_fft_set_support_tile(ig_fft* plan, int tile);
  * not -- 277) take it: the shift moves the origin of their input (forward) or output (inverse) weights and of the convolution kernel,
  * at no cost per pass.  IG_ERR_UNSUPPORTED on any other axis (shift 0 is always accepted).                                          */
 int  ig_fft_set_axis_shift(ig_fft* plan, int axis, int64_t shift);
+/* host: the z-contiguous y <-> z intermediate of a zero-padded plan of the coil-interleaved layout, [kx tile][ky][z'][piece]:
+ * its size and the byte offset of coil `coil` of the point (kx, ky, z) -- z counted from the image box's first plane -- for a
+ * grid dims[3], an image box box_dims[3], `coils` interleaved coils and pieces of piece_bytes (the z pass's tile: 256 bytes on a
+ * 512-point z axis, else 128).  -1 for arguments outside the geometry.                                                       */
+int64_t ig_fft_zc_size(const int64_t* dims, const int64_t* box_dims, int64_t coils, int64_t piece_bytes);
+int64_t ig_fft_zc_offset(const int64_t* dims, const int64_t* box_dims, int64_t coils, int64_t piece_bytes, int64_t kx, int64_t ky, int64_t z, int64_t coil);
 int  ig_fft_support_words(int64_t n2, int* zw_in, int* zw_out);        /* host; IG_ERR_UNSUPPORTED: no zero-pad-aware z pass */
 /* what ig_fft_plan_padded would run an axis of n points with: 3 = the power-of-two kernel (256, 512; any layout), 4 = the A x B
  * kernel (smooth lengths 128 ... 640; coil-interleaved layout), 5 = chirp-z (Bluestein) over an A x B length m >= 2 n - 1 for

@@ -146,6 +146,8 @@ PROTOTYPES = {
     "ig_grid_support":    (c_int, [c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_void_p]),
     "ig_fft_support_words": (c_int, [c_int64, POINTER(c_int), POINTER(c_int)]),
     "ig_fft_padded_axis_kind": (c_int, [c_int64, POINTER(c_int)]),
+    "ig_fft_zc_size":     (c_int64, [POINTER(c_int64), POINTER(c_int64), c_int64, c_int64]),
+    "ig_fft_zc_offset":   (c_int64, [POINTER(c_int64), POINTER(c_int64), c_int64, c_int64, c_int64, c_int64, c_int64, c_int64]),
     "ig_interp3_sep_words": (c_int, [c_int]),
     "ig_interp3_sep":     (c_int, [c_int64, POINTER(c_int64), c_double, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double,
                                    c_int, c_void_p]),

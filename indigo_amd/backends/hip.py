@@ -103,7 +103,8 @@ class HipBackend(Backend):
 
     def set_option(self, name, value):
         """plan options of the library (ig_set_option): 'fft.kernels' = 0 all kernels, 1 no A x B passes, 2 generic stages only;
-        takes effect for plans made afterwards (cached plans are dropped)"""
+        'fft.zc_intermediate' = 1 the fused SENSE leaf keeps what its y and z passes exchange z-contiguous per kx tile, 0 in the
+        grid's own order (bit-identical results, same workspace); takes effect for plans made afterwards (cached plans are dropped)"""
         self._check(self._L.ig_set_option(self._ctx, name.encode(), int(value)), "ig_set_option(%s)" % name)
         for entry in self._plans.values():
             self._L.ig_fft_destroy(entry[0])

@@ -34,6 +34,9 @@ struct ig_ctx {
     // plan options (ig_set_option): which transform kernels a NEW plan may use.  0 = all; 1 = no register-resident A x B passes
     // (their lengths fall back to the multi-stage LDS kernel); 2 = only the one-stage-per-launch generic kernel
     int          opt_fft_kernels = 0;
+    // "fft.zc_intermediate" (read by every zero-padded / cropped transform, not only by new plans): 1 = the fused SENSE leaf keeps
+    // what its y and z passes exchange z-contiguous per kx tile (ig_fft_zc.h), 0 = in the grid's own order
+    int          opt_fft_zc = 1;
     bool         bricks_attr = false;     // the brick-binned gridding kernel's dynamic-LDS opt-in was applied on this device
     bool         fft3d_attr = false;      // the two-launch 256^3 transform's dynamic-LDS opt-in was applied on this device
     bool         fft_w32_attr = false;    // the 32-column FFT kernels' dynamic-LDS opt-in was applied on this device

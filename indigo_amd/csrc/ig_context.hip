@@ -195,6 +195,11 @@ int ig_set_option(ig_ctx* ctx, const char* name, int64_t value) {
         ctx->opt_fft_kernels = (int)value;
         return IG_OK;
     }
+    if (std::string(name) == "fft.zc_intermediate") {
+        IG_REQUIRE(ctx, value == 0 || value == 1, "ig_set_option: fft.zc_intermediate is 0 (the grid's order) or 1 (z-contiguous per kx tile)");
+        ctx->opt_fft_zc = (int)value;
+        return IG_OK;
+    }
     return ig_fail(ctx, IG_ERR_ARG, "ig_set_option: unknown option '%s'", name);
 }
 

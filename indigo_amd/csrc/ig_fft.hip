@@ -37,6 +37,7 @@
 #include "ig_packed.h"
 #include "ig_fft_ab.h"
 #include "ig_fft_ab_list.h"
+#include "ig_fft_zc.h"
 #include <array>
 #include <vector>
 #include <functional>
@@ -415,8 +416,16 @@ k_fft_2stage(PassDesc d, const float2* __restrict__ tw) {
     // last tile are predicated without a branch, so all loads of a stage issue back to back.
     // Strided passes re-base the descriptor for every group of 16 elements along the axis (a pure SGPR add), so a
     // column may span far more than the 2 GB window (y pass of the interleaved layout: 16 MB per element step).
-    const float2* const b_in = d.in + (k0u * d.in_s[0] + (int64_t)k1 * d.in_s[1] + (int64_t)k2 * d.in_s[2]);
-    float2* const b_out = d.out + (k0u * d.out_s[0] + (int64_t)k1 * d.out_s[1] + (int64_t)k2 * d.out_s[2]);
+    // (a side stored piece by piece -- the z-contiguous y <-> z intermediate, ig_fft_zc.h -- places the tile's first column by
+    // piece and column of the piece: scalar arithmetic of the workgroup's head, nothing per lane or per element)
+    int64_t o_in = k0u * d.in_s[0], o_out = k0u * d.out_s[0];
+    if (BOXED && !AXIS0 && WMODE == 0 && d.zc_log2) {
+        const int64_t q = k0u >> d.zc_log2, e = k0u - (q << d.zc_log2);
+        if (d.in_zt) o_in = q * d.in_zt + e;
+        if (d.out_zt) o_out = q * d.out_zt + e;
+    }
+    const float2* const b_in = d.in + (o_in + (int64_t)k1 * d.in_s[1] + (int64_t)k2 * d.in_s[2]);
+    float2* const b_out = d.out + (o_out + (int64_t)k1 * d.out_s[1] + (int64_t)k2 * d.out_s[2]);
     const float2* const b_w = WMODE ? d.w + (k0u * d.w_s[0] + (int64_t)k1 * d.w_s[1] + (int64_t)k2 * d.w_s[2]) : nullptr;
     const rsrc_t r_in = make_rsrc(b_in), r_out = make_rsrc(b_out), r_w = make_rsrc(b_w);
     // x-axis passes run along contiguous memory by construction: unit strides known at compile time
@@ -1259,6 +1268,41 @@ static int pass_tiles(ig_ctx* ctx, PassDesc& d, int64_t cpt, int64_t reach, bool
     return IG_OK;
 }
 
+// Which instantiation a two-stage pass takes: whether it is boxed, its compile-time half box (HALF of k_fft_2stage) and
+// whether it runs on 32-column tiles.  (PassDesc::wide fixes the width where the caller has to know it beforehand: the
+// z-contiguous intermediate is laid out by the z pass's tile width, and its strides must not change the choice.)
+static bool two_stage_variant(const AxisPlan& ax, const PassDesc& d, bool axis0, int wmode, bool& boxed, int& half) {
+    boxed = d.tile_range || !(d.in_lo <= 0 && d.in_hi >= (int)ax.n && d.out_lo <= 0 && d.out_hi >= (int)ax.n);
+    // the image box of a 2x-oversampled grid sits at [n/4, 3n/4): compile-time-pruned variants
+    const int qn = (int)ax.n / 4;
+    half = 0;
+    if (boxed) {
+        const bool in_full = d.in_lo <= 0 && d.in_hi >= (int)ax.n, out_full = d.out_lo <= 0 && d.out_hi >= (int)ax.n;
+        if (d.in_lo == qn && d.in_hi == 3 * qn && !(d.tile_range && d.tile_range_mode == 2))
+            half = (out_full && !d.tile_range && !d.tile_bits) ? 3 : 1;
+        else if (d.out_lo == qn && d.out_hi == 3 * qn && !(d.tile_range && d.tile_range_mode == 1))
+            half = (in_full && !d.tile_range && !d.tile_bits) ? 4 : 2;
+        if (wmode == 1 && half != 3) half = 0;      // weighted variants exist for the fully static boxes only
+        if (wmode >= 2 && half != 4) half = 0;
+        if (((half == 1 || half == 3) && d.inverse) || ((half == 2 || half == 4) && !d.inverse)) half = 0;   // direction is baked in
+    }
+    // 32-column tiles (256-byte segments) pay where a side of the pass runs at a huge stride (y passes of the
+    // interleaved layout, 16 MB per element: -11...-15 %), for the half-input variants, which fit 128 VGPRs, and -- since
+    // round 3 skips the load instructions no lane wants -- for the half-output variants too (cropped z pass 1.28 -> 1.20 ms;
+    // before that skip the wider tile lost there: 1.63 against 1.50 ms).
+    const bool big_stride = (d.in_sj > d.out_sj ? d.in_sj : d.out_sj) * 8 >= (1 << 20);
+    // boxed passes WITHOUT a compile-time half box (e.g. the 320-point box of a 512-point axis, oversampling 1.6) also take
+    // 32-column tiles when one side runs at a huge stride: cropped y pass of config 5 0.85 -> 0.74 ms, padded y pass unchanged
+    // ... and so do plain (unboxed) passes at a huge stride, through the same run-time-box variant: the z pass of a plain 512^3
+    // transform steps 2 MB per element (3.82 -> 3.08 ms for 512^3 x 8)
+    // ... and the z passes of such a box once the support bitmap gates their loads / stores (config 5: see DESIGN 3.1)
+    const bool w32_generic = half == 0 && (big_stride || d.tile_bits != nullptr);
+    const bool w32 = (ax.n == 512 && !axis0 && wmode == 0 && !d.cw && d.ext0 % 32 == 0 &&
+        (half == 1 || half == 3 || half == 2 || half == 4 || w32_generic) &&
+        (!d.tile_range || d.tile_shift >= 1));
+    return d.wide ? d.wide == 2 : w32;
+}
+
 // launch one 2-stage axis pass (n in {256, 512}); axis0 selects the lane mapping for contiguous columns
 int launch_2stage(ig_ctx* ctx, const AxisPlan& ax, const PassDesc& d_in, bool axis0, int wmode) {
     PassDesc d = d_in;
@@ -1283,34 +1327,9 @@ int launch_2stage(ig_ctx* ctx, const AxisPlan& ax, const PassDesc& d_in, bool ax
         else if (wmode == 1) { if (half == 3) IG_2S(R1_, AX0_, 1, true, 3); else IG_2S(R1_, AX0_, 1, true, 0); } \
         else { if (half == 4) IG_2S(R1_, AX0_, 2, true, 4); else IG_2S(R1_, AX0_, 2, true, 0); }      \
     } while (0)
-    const bool boxed = d.tile_range || !(d.in_lo <= 0 && d.in_hi >= (int)ax.n && d.out_lo <= 0 && d.out_hi >= (int)ax.n);
-    // the image box of a 2x-oversampled grid sits at [n/4, 3n/4): compile-time-pruned variants
-    const int qn = (int)ax.n / 4;
-    int half = 0;
-    if (boxed) {
-        const bool in_full = d.in_lo <= 0 && d.in_hi >= (int)ax.n, out_full = d.out_lo <= 0 && d.out_hi >= (int)ax.n;
-        if (d.in_lo == qn && d.in_hi == 3 * qn && !(d.tile_range && d.tile_range_mode == 2))
-            half = (out_full && !d.tile_range && !d.tile_bits) ? 3 : 1;
-        else if (d.out_lo == qn && d.out_hi == 3 * qn && !(d.tile_range && d.tile_range_mode == 1))
-            half = (in_full && !d.tile_range && !d.tile_bits) ? 4 : 2;
-        if (wmode == 1 && half != 3) half = 0;      // weighted variants exist for the fully static boxes only
-        if (wmode >= 2 && half != 4) half = 0;
-        if (((half == 1 || half == 3) && d.inverse) || ((half == 2 || half == 4) && !d.inverse)) half = 0;   // direction is baked in
-    }
-    // 32-column tiles (256-byte segments) pay where a side of the pass runs at a huge stride (y passes of the
-    // interleaved layout, 16 MB per element: -11...-15 %), for the half-input variants, which fit 128 VGPRs, and -- since
-    // round 3 skips the load instructions no lane wants -- for the half-output variants too (cropped z pass 1.28 -> 1.20 ms;
-    // before that skip the wider tile lost there: 1.63 against 1.50 ms).
-    const bool big_stride = (d.in_sj > d.out_sj ? d.in_sj : d.out_sj) * 8 >= (1 << 20);
-    // boxed passes WITHOUT a compile-time half box (e.g. the 320-point box of a 512-point axis, oversampling 1.6) also take
-    // 32-column tiles when one side runs at a huge stride: cropped y pass of config 5 0.85 -> 0.74 ms, padded y pass unchanged
-    // ... and so do plain (unboxed) passes at a huge stride, through the same run-time-box variant: the z pass of a plain 512^3
-    // transform steps 2 MB per element (3.82 -> 3.08 ms for 512^3 x 8)
-    // ... and the z passes of such a box once the support bitmap gates their loads / stores (config 5: see DESIGN 3.1)
-    const bool w32_generic = half == 0 && (big_stride || d.tile_bits != nullptr);
-    if (ax.n == 512 && !axis0 && wmode == 0 && !d.cw && d.ext0 % 32 == 0 &&
-        (half == 1 || half == 3 || half == 2 || half == 4 || w32_generic) &&
-        (!d.tile_range || d.tile_shift >= 1)) {
+    bool boxed; int half;
+    const bool w32 = two_stage_variant(ax, d, axis0, wmode, boxed, half);
+    if (w32) {
         // 32-column tiles: 256-byte segments per row, 512 threads, 69.6 KB of LDS (2 workgroups per CU)
         PassDesc d2 = d;
         if (d2.tile_range) d2.tile_shift = d.tile_shift - 1;
@@ -1967,11 +1986,44 @@ static PassDesc pass_z(const PaddedGeom& g, bool inverse, const PaddedBufs& m, c
     return d;
 }
 
+// The y <-> z intermediate of the coil-interleaved layout, z-contiguous per kx tile (ig_fft_zc.h; plan option "fft.zc_intermediate"):
+// re-addresses the side of the y pass and of the z pass that holds it -- padded: y writes, z reads; cropped: z writes, y reads --
+// as the array `zc` in the order [kx tile][ky][z'][piece], a piece being the z pass's tile.  Both passes keep the tile width the
+// grid's own order gives them (PassDesc::wide), so the kernels and their instantiations are the ones that run without it; only
+// the strides, the base pointers and the tile's origin (PassDesc::zc_log2, in_zt / out_zt) differ.  Taken where both axes run the
+// two-stage kernel and a y tile lies inside one piece; every other route keeps the grid's order.  z0: first image plane of the
+// y pass's slab.  Returns whether the passes were re-addressed.
+static bool zc_route(const ig_fft* p, const PaddedGeom& g, float2* zc, bool inverse, int64_t z0, PassDesc& dy, PassDesc& dz) {
+    if (!p->ctx->opt_fft_zc || !g.interleaved || !zc || p->axis[1].kind != 3 || p->axis[2].kind != 3) return false;
+    bool by, bz; int half;
+    const bool wy = two_stage_variant(p->axis[1], dy, false, 0, by, half), wz = two_stage_variant(p->axis[2], dz, false, 0, bz, half);
+    if (!by || !bz || (wy && !wz)) return false;          // (only the boxed instantiations read the piece fields)
+    const ZcGeom z{g.n[0], g.n[1], g.b[2], g.C, wz ? 32 : 16};
+    if (!zc_valid(z)) return false;
+    const ZcSide sy = zc_side(z, 1), sz = zc_side(z, 2);
+    // the y pass: columns (k0, z'), all ky; the z pass: columns (k0, ky), z in the box -- its base is that of plane z = 0
+    float2* const y_base = zc + zc_offset(z, 0, 0, z0, 0);
+    float2* const z_base = zc - g.l[2] * sz.sj;
+    if (!inverse) {
+        dy.out = y_base; dy.out_sj = sy.sj; dy.out_s[0] = 1; dy.out_s[1] = sy.s1; dy.out_s[2] = 0; dy.out_zt = sy.zt;
+        dz.in = z_base;  dz.in_sj = sz.sj;  dz.in_s[0] = 1;  dz.in_s[1] = sz.s1;  dz.in_s[2] = 0;  dz.in_zt = sz.zt;
+    } else {
+        dz.out = z_base; dz.out_sj = sz.sj; dz.out_s[0] = 1; dz.out_s[1] = sz.s1; dz.out_s[2] = 0; dz.out_zt = sz.zt;
+        dy.in = y_base;  dy.in_sj = sy.sj;  dy.in_s[0] = 1;  dy.in_s[1] = sy.s1;  dy.in_s[2] = 0;  dy.in_zt = sy.zt;
+    }
+    dy.zc_log2 = dz.zc_log2 = sz.piece_log2;
+    dy.wide = wy ? 2 : 1; dz.wide = wz ? 2 : 1;
+    return true;
+}
+
 static int exec_padded(ig_fft* p, float2* x, int64_t x_bstride, const float2* w, float2* y, float2* work, const short2* support) {
     ig_ctx* ctx = p->ctx;
     const PaddedGeom g = padded_geom(p, false, x_bstride, false);
     const PaddedBufs m = padded_bufs(p, g, x, y, y, work);
     const int64_t plane = g.n[0] * g.n[1], b2 = g.b[2];
+    // (the z-contiguous intermediate takes the head of the workspace, which the padded transform otherwise leaves alone)
+    PassDesc dy = pass_y(g, false, m, support, 0, b2), dz = pass_z(g, false, m, support);
+    zc_route(p, g, work, false, 0, dy, dz);
     {
         ig_prof_scope prof(ctx, "fft_pad_x", (double)(g.bvol + (w ? g.bvol : 0) + g.cvol) * g.C * 8.0);
         int wmode; bool axis0;
@@ -1980,11 +2032,11 @@ static int exec_padded(ig_fft* p, float2* x, int64_t x_bstride, const float2* w,
     }
     {
         ig_prof_scope prof(ctx, "fft_pad_y", (double)(g.cvol + plane * b2) * g.C * 8.0);
-        if (int rc = launch_pass(ctx, p->axis[1], pass_y(g, false, m, support, 0, b2), false, 0)) return rc;
+        if (int rc = launch_pass(ctx, p->axis[1], dy, false, 0)) return rc;
     }
     {
         ig_prof_scope prof(ctx, "fft_pad_z", (double)(plane * b2 + g.vol) * g.C * 8.0);
-        if (int rc = launch_pass(ctx, p->axis[2], pass_z(g, false, m, support), false, 0)) return rc;
+        if (int rc = launch_pass(ctx, p->axis[2], dz, false, 0)) return rc;
     }
     return IG_OK;
 }
@@ -1997,14 +2049,16 @@ static int exec_cropped(ig_fft* p, float2* y, const float2* w, float2* x, int64_
     const PaddedBufs m = padded_bufs(p, g, x, y, work, work);
     const int64_t plane = g.n[0] * g.n[1], b2 = g.b[2];
     const int64_t nz = z1 - z0;                      // image planes the y and x passes cover
+    PassDesc dy = pass_y(g, true, m, support, z0, nz > 0 ? nz : 0), dz = pass_z(g, true, m, support);
+    zc_route(p, g, work, true, z0, dy, dz);
     if (phases & 1) {
         ig_prof_scope prof(ctx, "fft_crop_z", (double)(g.vol + plane * b2) * g.C * 8.0);
-        if (int rc = launch_pass(ctx, p->axis[2], pass_z(g, true, m, support), false, 0)) return rc;
+        if (int rc = launch_pass(ctx, p->axis[2], dz, false, 0)) return rc;
     }
     if (!(phases & 2) || nz <= 0) return IG_OK;
     {
         ig_prof_scope prof(ctx, "fft_crop_y", (double)(plane * nz + g.n[0] * g.b[1] * nz) * g.C * 8.0);
-        if (int rc = launch_pass(ctx, p->axis[1], pass_y(g, true, m, support, z0, nz), false, 0)) return rc;
+        if (int rc = launch_pass(ctx, p->axis[1], dy, false, 0)) return rc;
     }
     {
         const double bytes = sum_coils ? (double)(g.cvol + g.bvol) * g.C * 8.0 + (double)g.bvol * 8.0 : (double)(g.cvol + g.bvol + (w ? g.bvol : 0)) * g.C * 8.0;
@@ -2014,6 +2068,21 @@ static int exec_cropped(ig_fft* p, float2* y, const float2* w, float2* x, int64_
         if (int rc = launch_pass(ctx, p->axis[0], d, axis0, wmode)) return rc;
     }
     return IG_OK;
+}
+
+// The z-contiguous y <-> z intermediate (ig_fft_zc.h) as the passes address it: bytes, complex64 elements.  dims: the grid;
+// box_dims: the image box; piece_bytes: the z pass's tile, 128 or 256.  -1: arguments outside the geometry.
+int64_t ig_fft_zc_size(const int64_t* dims, const int64_t* box_dims, int64_t coils, int64_t piece_bytes) {
+    if (!dims || !box_dims || piece_bytes < 8 || piece_bytes % 8) return -1;
+    const ZcGeom z{dims[0], dims[1], box_dims[2], coils, piece_bytes / 8};
+    return zc_valid(z) && box_dims[2] <= dims[2] ? zc_size(z) * 8 : -1;
+}
+
+int64_t ig_fft_zc_offset(const int64_t* dims, const int64_t* box_dims, int64_t coils, int64_t piece_bytes, int64_t kx, int64_t ky, int64_t z, int64_t coil) {
+    if (ig_fft_zc_size(dims, box_dims, coils, piece_bytes) < 0) return -1;
+    const ZcGeom g{dims[0], dims[1], box_dims[2], coils, piece_bytes / 8};
+    if (kx < 0 || kx >= g.n0 || ky < 0 || ky >= g.n1 || z < 0 || z >= g.b2 || coil < 0 || coil >= g.C) return -1;
+    return zc_offset(g, kx, ky, z, coil) * 8;
 }
 
 int ig_fft_support_words(int64_t n, int* zw_in, int* zw_out) {

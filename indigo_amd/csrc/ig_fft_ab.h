@@ -60,6 +60,13 @@ struct PassDesc {
     // optional: tiles whose k1 lies outside k1_range[tile >> tile_shift] = [lo, hi) are skipped altogether (the
     // cropped z pass: the y pass that follows never reads ky outside the kx tile's ky hull)
     const short2* k1_range;
+    // optional (k_fft_2stage, strided passes without a lane split): a side whose columns are stored piece by piece -- the
+    // z-contiguous y <-> z intermediate of the coil-interleaved layout, ig_fft_zc.h.  zc_log2 > 0: a piece is 2^zc_log2 columns
+    // (a multiple of the tile); on a side with a non-zero in_zt / out_zt the tile's first column k0 lies at
+    // (k0 >> zc_log2) * zt + (k0 & (2^zc_log2 - 1)) in place of k0 * s[0].  Lanes, k1, k2 and the transform axis as ever.
+    int zc_log2;
+    int64_t in_zt, out_zt;
+    int wide;                   // k_fft_2stage: 0 = the launcher picks the tile width by the strides; 1 = 16, 2 = 32 columns
 };
 
 
