@@ -272,6 +272,21 @@ int  ig_basis_c64(ig_ctx* ctx, int64_t n, int64_t nk, int64_t nt, const void* ph
  * One pass: 16 n nc nk + 4 nk^2 n bytes.                                                                                  */
 int  ig_psf_mix_c64(ig_ctx* ctx, int64_t n, int64_t nc, int64_t nk, const float* kern, const void* x, int64_t ldx,
                     void* y, int64_t ldy, int64_t sg, int64_t sc);
+/* The per-voxel coil-map product of soft-SENSE -- nm sets of maps, nm images -- and its adjoint (operators.CoilMaps,
+ * operators.ZpadFFTMaps, Backend.coil_maps, pics on a scan whose maps have a MAPS axis).  No reference counterpart.
+ *   adjoint == 0:  y[i, c] = beta*y[i, c] + alpha * sum_m      S[i, c, m]  * x[i, m]     (x: the images, y: the coil images)
+ *   adjoint != 0:  y[i, m] = beta*y[i, m] + alpha * sum_c conj(S[i, c, m]) * x[i, c]     (x: the coil images, y: the images)
+ * i < n voxels, c < nc coils, m < nm.  The images are a device column-major panel of nm columns, ldi >= n in elements; rows between
+ * the columns are never touched.  The coil images are coil-major, element (i, c) at i + sc*c (sg = 1, sc >= n, any nc >= 1), or
+ * coil-interleaved, element (i, c) at i*sg + c (sc = 1, sg = the row width 2, 4, 8 or 16, nc <= sg: the form of the layout-2 weights
+ * of ig_fft_exec_padded and of the layout-2 result of ig_fft_exec_cropped).  Slots c >= nc of a row are zero-weight padding coils:
+ * forward writes them as zero, adjoint never reads them, in x or in maps.  maps is nm dense planes in the form of the coil images:
+ * n*nc elements each (element (i, c) at i + n*c), or n*sg.
+ * beta == 0: y is not read.  A y that overlaps x or maps is IG_ERR_ARG, with nothing written.  1 <= nm <= 4, n >= 1, nc >= 1 and
+ * the strides above, else IG_ERR_UNSUPPORTED.  One pass: 8 n (nc nm + nc + nm) bytes, and 8 n (nc or nm: the rows of y) more when
+ * beta != 0.                                                                                                                    */
+int  ig_coil_maps_c64(ig_ctx* ctx, int64_t n, int64_t nc, int64_t nm, const void* maps, int adjoint, const void* x,
+                      float alpha_re, float alpha_im, float beta_re, float beta_im, void* y, int64_t ldi, int64_t sg, int64_t sc);
 
 /* ------------------------------------------------------------------------
  * CSR x dense-panel SpMM.  Replaces Backend.ccsrmm

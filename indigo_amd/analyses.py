@@ -45,6 +45,9 @@ class Memusage(Visitor):
     def visit(self, node):
         # pre-order bookkeeping with scoped pushes, so do not use Visitor's post-order dispatch
         self._peak = max(self._peak, sum(self._live))
+        if isinstance(node, op.ZpadFFTMaps) and id(node) not in self._seen:
+            self._seen.add(id(node))
+            self._base += node.maps_bytes()
         if isinstance(node, (op.Product, op.UnscaledFFT, op.ZpadFFT, op.HeadRows)):
             with self._push(self._live, self._round(node._mem_usage(self._ncols()))):
                 self._peak = max(self._peak, sum(self._live))
@@ -63,7 +66,7 @@ class Memusage(Visitor):
             if id(node) not in self._seen:
                 self._seen.add(id(node))
                 self._base += (node.shape[0] + 1) * 4 + node.nnz * 4 + node.nnz * 8
-        elif isinstance(node, (op.DenseMatrix, op.FrameBasis)):
+        elif isinstance(node, (op.DenseMatrix, op.FrameBasis, op.CoilMaps)):
             if id(node) not in self._seen:
                 self._seen.add(id(node))
                 self._base += node._matrix.nbytes

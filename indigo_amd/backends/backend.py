@@ -488,6 +488,15 @@ class Backend(object):
         coefficient-major in, T frames stacked frame-major out (see operators.FrameBasis); .H is its adjoint"""
         return op.FrameBasis(self, phi, n, **kwargs)
 
+    def CoilMaps(self, maps, **kwargs):
+        """the soft-SENSE map stack for the host array `maps` = dims + (C, M), shape (N C, N M): M images stacked map-major in, C
+        coil images stacked coil-major out (see operators.CoilMaps); .H is its adjoint"""
+        return op.CoilMaps(self, maps, **kwargs)
+
+    def ZpadFFTMaps(self, grid_shape, box_shape, weights, maps, ncoils, **kwargs):
+        """the fused ZpadFFT leaf with M images on its image side (see operators.ZpadFFTMaps)"""
+        return op.ZpadFFTMaps(self, grid_shape, box_shape, weights, maps, ncoils, **kwargs)
+
     def Interp(self, N, coord, width, table, dtype=_C64, **kwargs):
         """gridding / interpolation matrix (npts x prod N) from a k-space trajectory"""
         assert len(N) == 3
@@ -785,6 +794,43 @@ class Backend(object):
         out = (v @ p.conj() if adjoint else v @ p.T) * complex(alpha)
         if beta != 0:
             out = out + complex(beta) * y.to_host().reshape((n, cols_y), order='F')
+        y.copy_from(np.asfortranarray(out.astype(_C64).reshape(y.shape, order='F')))
+
+    def coil_maps(self, y, x, maps, n, ncoils, nmaps, adjoint=False, alpha=1, beta=0, interleaved=False, width=None):
+        """y = beta*y + alpha * S x (adjoint: S^H x), the per-voxel coil-map product of soft-SENSE between M = `nmaps` images and
+        C = `ncoils` coil images of `n` voxels:  forward y[i, c] = sum_m S[i, c, m] x[i, m], adjoint
+        y[i, m] = sum_c conj(S[i, c, m]) x[i, c].  The images are an n x M panel, or the same as an (n M, 1) vector, image m in rows
+        [mn, (m+1)n).  The coil images are an n x C panel or the (n C, 1) vector (element (i, c) at i + n c), or, `interleaved`, one
+        contiguous array whose memory holds the `width` >= C coil slots of a voxel side by side (element (i, c) at i width + c; width
+        2, 4, 8 or 16): slots c >= C are zero-weight padding coils, written as zero on forward and never read on adjoint.  maps is a
+        backend array of M dense planes in the form of the coil images (n C elements each, or n width).  beta == 0: y is not read; y
+        must not overlap x or maps; M <= 4.  Host form in float64 through to_host / copy_from; device backends override it."""
+        n, C, M = int(n), int(ncoils), int(nmaps)
+        if not 1 <= M <= 4:
+            raise RuntimeError("coil_maps: %d sets of maps, between 1 and 4 are supported" % M)
+        w = int(width) if (interleaved and width is not None) else C
+        if interleaved and (w not in (2, 4, 8, 16) or C > w):
+            raise RuntimeError("coil_maps: %d coils in interleaved rows of width %d (2, 4, 8 or 16, at least the coils)" % (C, w))
+        assert n >= 1 and C >= 1 and maps.size == n * w * M, (maps.shape, n, w, M)
+        img, coil = (y, x) if adjoint else (x, y)
+        assert img.size == n * M and coil.size == n * w, (x.shape, y.shape, n, w, M)
+        cshape = (w, n) if interleaved else (n, w)
+        S = maps.to_host().reshape(cshape + (M,), order='F').astype(np.complex128)
+        S = (S.transpose(1, 0, 2) if interleaved else S)[:, :C]                       # (n, C, M)
+        v = x.to_host().reshape(cshape if adjoint else (n, M), order='F').astype(np.complex128)
+        if adjoint:
+            v = (v.T if interleaved else v)[:, :C]
+            out = np.einsum('icm,ic->im', S.conj(), v) * complex(alpha)
+            if beta != 0:
+                out = out + complex(beta) * y.to_host().reshape((n, M), order='F')
+        else:
+            prod = np.einsum('icm,im->ic', S, v) * complex(alpha)
+            if beta != 0:
+                old = y.to_host().reshape(cshape, order='F')
+                prod = prod + complex(beta) * (old.T if interleaved else old)[:, :C]
+            out = np.zeros((n, w), dtype=np.complex128)
+            out[:, :C] = prod
+            out = out.T if interleaved else out
         y.copy_from(np.asfortranarray(out.astype(_C64).reshape(y.shape, order='F')))
 
     @staticmethod

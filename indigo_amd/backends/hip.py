@@ -914,6 +914,27 @@ class HipBackend(Backend):
         self._check(self._L.ig_basis_c64(self._ctx, n, K, T, ctypes.c_void_p(phi._arr), phi._leading_dim, int(bool(adjoint)),
                                          xp, ldx, ar, ai, br, bi, yp, ldy), "ig_basis_c64")
 
+    def coil_maps(self, y, x, maps, n, ncoils, nmaps, adjoint=False, alpha=1, beta=0, interleaved=False, width=None):
+        """Backend.coil_maps on the device (ig_coil_maps_c64): the images and the coil-major coil images are the columns of panels
+        with their leading dimensions, or stacked in one column; interleaved coil images are one contiguous array"""
+        assert x.dtype == _C64 and y.dtype == _C64 and maps.dtype == _C64, "only complex64 is supported"
+        n, C, M = int(n), int(ncoils), int(nmaps)
+        w = int(width) if (interleaved and width is not None) else C
+        assert maps.contiguous and maps.size == n * w * M, (maps.shape, n, w, M)
+        img, coil = (y, x) if adjoint else (x, y)
+        ip, ldi = self._frame_panel(img, n, M)
+        if interleaved:
+            assert coil.contiguous and coil.size == n * w, (coil.shape, n, w)
+            cp, sg, sc = ctypes.c_void_p(coil._arr), w, 1
+        else:
+            cp, sc = self._frame_panel(coil, n, C)
+            sg = 1
+        xp, yp = (cp, ip) if adjoint else (ip, cp)
+        ar, ai = _cplx(alpha)
+        br, bi = _cplx(beta)
+        self._check(self._L.ig_coil_maps_c64(self._ctx, n, C, M, ctypes.c_void_p(maps._arr), int(bool(adjoint)), xp, ar, ai, br, bi,
+                                             yp, ldi, sg, sc), "ig_coil_maps_c64")
+
     def psf_mix(self, y, x, kern, n, ncoils, interleaved=False, width=None):
         """Backend.psf_mix on the device (ig_psf_mix_c64): the K images are the columns of panels with their leading
         dimensions, or stacked in one column; y may be x"""

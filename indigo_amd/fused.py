@@ -317,6 +317,7 @@ def assemble(backend, Gm, oN, N, weights_of, Cn, layout, chunks, table=None, box
                 Z = backend.ZpadFFT(oN, N, wts, box_lo=box_lo, layout=2, support=fine[w][0], support_tile=fine[w][1], name='fft*zpad*apod*maps', **kskw)
             else:
                 Z = backend.ZpadFFT(oN, N, wts, box_lo=box_lo, layout=2, support=table, name='fft*zpad*apod*maps', **kskw)
+            Z._coil_range = (lo, hi)          # (the coils of this chunk: what transforms.AttachCoilMaps cuts the maps of a soft-SENSE scan by)
             tree = backend.KronI(w, G_il) * Z
             if real < w:
                 # zero-weight padding coils: their k-space rows come last, are exact zeros on the way out and read as zeros on the way in
@@ -325,6 +326,7 @@ def assemble(backend, Gm, oN, N, weights_of, Cn, layout, chunks, table=None, box
             lay = layout if layout in (0, 1) else 1          # one coil (or an explicit per-coil layout): the per-coil kernels
             G_pc = G_pc or gridding(False, real)
             Z = backend.ZpadFFT(oN, N, weights_of(lo, hi), box_lo=box_lo, layout=lay, support=table if lay == 1 else None, name='fft*zpad*apod*maps')
+            Z._coil_range = (lo, hi)
             tree = backend.KronI(real, G_pc) * Z
         trees.append(tree)
     A = trees[0] if len(trees) == 1 else backend.VStack(trees, name='coil-chunks')

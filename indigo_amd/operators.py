@@ -484,6 +484,139 @@ class ZpadFFT(MatrixFreeOperator):
         return (N * C * 8 + 255) // 256 * 256 + self._ws_bytes()
 
 
+class ZpadFFTMaps(ZpadFFT):
+    """The fused leaf `ZpadFFT` with M images on its image side: soft-SENSE, M sets of coil maps, shape (C*P, N*M).
+
+        forward :  y[:, c] = FFT( zeropad( sum_m S'[:, c, m] * x_m ) )
+        adjoint :  x_m = sum_c conj(S'[:, c, m]) * crop( IFFT( y[:, c] ) )
+
+    The input is M images stacked map-major, image m in rows [mN, (m+1)N).  `weights` (box + (C,)) are the per-voxel weights of the
+    `ZpadFFT` this leaf replaces in a tree built from unit maps (modulation x roll-off x gridding constant, zero for the padding
+    coils of a chunk), `maps` (box + (ncoils, M)) the chunk's `ncoils` <= C real coils of every set: S' = weights x maps, padded
+    with zero coils to the chunk's width C.  Grid, box, layout, support table, support tile and kshift are `ZpadFFT`'s, and so are
+    the transform kernels: forward, `Backend.coil_maps` writes W = sum_m S'_m x_m into a scratch panel in the leaf's weight layout
+    and `fft_padded` transforms an image of ones with the weights W; adjoint, `ifft_cropped` with unit weights leaves the C cropped
+    coil images in a scratch panel (coil-interleaved for layout 2) and `coil_maps(adjoint=True)` combines them into the M images
+    with alpha and beta.  Forward expects beta == 0, as `ZpadFFT` does.  Scratch: one N x C panel and the transform's workspace."""
+
+    def __init__(self, backend, grid_shape, box_shape, weights, maps, ncoils, **kwargs):
+        super().__init__(backend, grid_shape, box_shape, weights, **kwargs)
+        real = int(ncoils)
+        maps = np.asarray(maps, dtype=_C64)
+        if maps.ndim != 5 or maps.shape[:3] != self._box or maps.shape[3] != real or not 1 <= real <= self._C:
+            raise ValueError("ZpadFFTMaps: maps must be box + (ncoils, sets) with ncoils <= %d, got shape %s for box %s and %d coils"
+                             % (self._C, maps.shape, self._box, real))
+        M = int(maps.shape[4])
+        if not 1 <= M <= 4:
+            raise ValueError("ZpadFFTMaps: %d sets of maps, between 1 and 4 are supported" % M)
+        self._real, self._M = real, M
+        N = int(np.prod(self._box))
+        w2 = self._w_h.reshape((N, self._C), order='F')
+        m2 = maps.reshape((N, real, M), order='F')
+        # M planes in the form of the leaf's weights: layout 2 a voxel's C slots side by side, else one coil image after the other
+        planes = np.zeros((M, N, self._C) if self._layout == 2 else (M, self._C, N), dtype=_C64)
+        for m in range(M):
+            prod = w2[:, :real] * m2[:, :, m]
+            if self._layout == 2:
+                planes[m, :, :real] = prod
+            else:
+                planes[m, :real, :] = prod.T
+        self._w_h = None
+        self._s_h, self._s_d, self._ones_d = planes.reshape(-1), None, None
+        self._shape = (self._shape[0], N * M)
+
+    def _maps(self):
+        if self._s_d is None:
+            self._s_d = self._backend.copy_array(self._s_h, name=self._name + '.maps')
+            self._s_h = None
+            N = int(np.prod(self._box))
+            self._ones_d = self._backend.copy_array(np.ones((N * self._C, 1), dtype=_C64), name=self._name + '.ones')
+        return self._s_d
+
+    def maps_bytes(self):
+        """device bytes of S' and of the unit weights"""
+        return int(np.prod(self._box)) * self._C * (self._M + 1) * 8
+
+    def _trace_maps(self, forward, beta):
+        trace = getattr(self._backend, 'trace', None)
+        if trace is not None:
+            N, C, M = int(np.prod(self._box)), self._real, self._M
+            trace.add('coil_maps', nbytes=8 * N * (C * M + C + M) + (0 if beta == 0 else 8 * N * M), nflops=8 * N * C * M,
+                      shape=(N, C, M), forward=forward, name=self._name + '.maps')
+
+    def _eval(self, y, x, alpha=1, beta=0, forward=True, left=True):
+        B = self._backend
+        P, N, C, M = int(np.prod(self._grid)), int(np.prod(self._box)), self._C, self._M
+        il = self._layout == 2
+        S = self._maps()
+        ncols = x.shape[1]
+        for j in range(ncols):
+            xj = x if ncols == 1 else x[:, j:j + 1]
+            yj = y if ncols == 1 else y[:, j:j + 1]
+            self._trace(forward)
+            self._trace_maps(forward, 0 if forward else beta)
+            if forward:
+                assert beta == 0, "ZpadFFTMaps forward expects beta == 0, got %s" % beta
+                with B.scratch(shape=(N * C, 1)) as W:
+                    B.coil_maps(W, xj, S, N, self._real, M, alpha=alpha, interleaved=il, width=C if il else None)
+                    ones = self._ones_d.dense_rows(0, N)
+                    if self._layout:
+                        with B.scratch(nbytes=self._ws_bytes()) as ws:
+                            B.fft_padded(yj.reshape((P, C)), ones, W, self._grid, self._lo, self._box, ws, self._layout,
+                                         self._support(), **self._tile_kw)
+                    else:
+                        B.fft_padded(yj.reshape((P, C)), ones, W, self._grid, self._lo, self._box)
+            else:
+                with B.scratch(shape=(N, C)) as tmp:
+                    with B.scratch(nbytes=self._ws_bytes()) as ws:
+                        B.ifft_cropped(tmp, xj.reshape((P, C)), self._ones_d, self._grid, self._lo, self._box, ws, self._layout,
+                                       self._support(), **self._tile_kw)
+                    B.coil_maps(yj, tmp, S, N, self._real, M, adjoint=True, alpha=alpha, beta=beta, interleaved=il, width=C if il else None)
+
+
+class CoilMaps(MatrixFreeOperator):
+    """The map stack of soft-SENSE: `maps` is a host array dims + (C, M), M sets of C coil maps on a volume of N voxels; shape
+    (N C, N M).  The input is M images stacked map-major, image m in rows [mN, (m+1)N); the output is C coil images stacked
+    coil-major, coil image c = sum_m maps[..., c, m] * image m in rows [cN, (c+1)N), as `KronI(C, NUFFT)` consumes them.  .H is the
+    adjoint, image m = sum_c conj(maps[..., c, m]) * coil image c.  M <= 4.  The maps go to the device once, on first evaluation.
+    With M = 1 it equals VStack(Diag(map_c)); it is the leaf of every soft-SENSE tree that does not run through `ZpadFFTMaps`
+    (DESIGN.md §3.12)."""
+
+    def __init__(self, backend, maps, **kwargs):
+        try:
+            maps = np.asarray(maps, dtype=_C64)
+        except (TypeError, ValueError):
+            raise ValueError("CoilMaps: the maps do not convert to complex64")
+        if maps.ndim < 3 or min(maps.shape) < 1:
+            raise ValueError("CoilMaps: maps must be dims + (coils, sets), got shape %s" % (maps.shape,))
+        C, M = int(maps.shape[-2]), int(maps.shape[-1])
+        if not 1 <= M <= 4:
+            raise ValueError("CoilMaps: %d sets of maps, between 1 and 4 are supported" % M)
+        self._n = int(np.prod(maps.shape[:-2]))
+        self._C, self._M = C, M
+        self._matrix = np.asfortranarray(maps.reshape((self._n * C * M, 1), order='F'))          # element (i, c, m) at i + n c + n C m
+        self._matrix_d = None
+        kwargs.setdefault('name', 'maps')
+        super().__init__(backend, shape=(self._n * C, self._n * M), **kwargs)
+
+    def _eval(self, y, x, alpha=1, beta=0, forward=True, left=True):
+        if self._matrix_d is None:
+            self._matrix_d = self._backend.copy_array(self._matrix, name=self._name)
+        n, C, M = self._n, self._C, self._M
+        trace = getattr(self._backend, 'trace', None)
+        if trace is not None:
+            # a single pass: every map, every coil image and every image moves once (8 B per voxel each); beta != 0 reads the output
+            trace.add('coil_maps', nbytes=8 * n * (C * M + C + M) * x.shape[1] + (0 if beta == 0 else y.nbytes), nflops=8 * n * C * M * x.shape[1],
+                      shape=x.shape, forward=forward, name=self._name)
+        if x.shape[1] == 1:
+            return self._backend.coil_maps(y, x, self._matrix_d, n, C, M, adjoint=not forward, alpha=alpha, beta=beta)
+        for j in range(x.shape[1]):             # the images become the columns of a panel inside: one product per column
+            self._backend.coil_maps(y[:, j:j + 1], x[:, j:j + 1], self._matrix_d, n, C, M, adjoint=not forward, alpha=alpha, beta=beta)
+
+    def _mem_usage(self, ncols):
+        return 0            # (no scratch: the maps themselves are counted with the matrices, analyses.Memusage)
+
+
 class AxisPermute(MatrixFreeOperator):
     """Relabelling of the axes of an F-ordered image volume of shape `dims`: output axis a is input axis perm[a], i.e.
     y = x.reshape(dims, order='F').transpose(perm).ravel(order='F');  the adjoint is the inverse permutation.  Pure data

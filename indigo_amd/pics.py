@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Parallel-imaging reconstruction driver: non-Cartesian SENSE by conjugate gradients, L1-wavelet or locally low-rank FISTA, or
-total-variation primal-dual; time frames one by one or in a temporal subspace.
+total-variation primal-dual; time frames one by one or in a temporal subspace; soft-SENSE on scans with several sets of coil maps.
 
     python -m indigo_amd.pics [-i ITER] [--lamda L] [-O LEVEL] [--crop "COIL:2,TIME:1"] [--no-fuse] scan.h5 | scan.npz
     python -m indigo_amd.pics --l1 LAMBDA [--wavelet db2] [--levels 3] [--step S | --power-iters 15] ... scan.npz
@@ -9,6 +9,7 @@ total-variation primal-dual; time frames one by one or in a temporal subspace.
     python -m indigo_amd.pics --llr LAMBDA [--llr-block 8] [--llr-shifts [--llr-seed 0]] [--tv MU] [--tv-time MU_T] ... frames.npz
     python -m indigo_amd.pics --basis PHI.npy [--basis-rank K] [--l1 LAMBDA | --llr LAMBDA] [--tv MU] ... frames.npz
     python -m indigo_amd.pics --toeplitz [--basis PHI.npy ...] ... scan.npz | frames.npz        (A^H A as one Toeplitz operator)
+    python -m indigo_amd.pics [--l1 | --tv | --llr ...] [--crop "MAPS:1"] espirit.npz           (maps with a MAPS axis of length M: soft-SENSE)
 
 The counterpart of the reference's driver script (examples/pics.py:20-95 arguments, data layout and tree
 construction, :179-233 recipe, normal equations, CG, output): reads `data` (k-space), `maps` (coil sensitivities)
@@ -85,6 +86,23 @@ A and A^H y stay the gridding operator, which is used once; CG, `--l1`, `--tv`, 
 run unchanged on the new A^H A.  The two forms of A^H A differ by the NUFFT's own approximation error (the gridding form carries
 it twice, the Toeplitz form once).  Without `--toeplitz` the driver runs the code it ran before.
 
+Soft-SENSE.  A scan whose `maps` carry a MAPS axis of length M > 1 (`bart ecalib` writes two sets by default; `data` keeps MAPS = 1)
+is reconstructed as `bart pics` does: the unknown of a frame is M images, one per set,
+
+    y_c = NUFFT( sum_m S_{c,m} . x_m ),        (A^H y)_m = sum_c conj(S_{c,m}) . NUFFT^H y_c        (M <= 4)
+
+the remedy for a field of view smaller than the object, for phase singularities and for motion-corrupted calibration.  The
+transforms and the gridding do not depend on M, only the per-voxel C x M map product does (`Backend.coil_maps`):
+where `FuseZpadFFT` fuses the tree, its `ZpadFFT` leaves become `operators.ZpadFFTMaps` (`transforms.soft_sense_tree`); at -O0..2,
+with --no-fuse, on grids the fused leaf refuses and on grids it takes only behind an image permutation A is
+Optimize(recipe)(KronI(C, NUFFT)) * operators.CoilMaps(maps).  The M images of a frame are stacked map-major, the frames stay
+frame-major around them, and the result is (X, Y, Z, 1, M[, 1, ..., T]).  The solvers run on the N M T unknown as they are: CG
+jointly, `--l1` on every image, `--tv` the spatial term on every image (M T columns, no coupling between them), `--llr` on the (block
+voxels) x (M T) matrices (M T <= 32), which is what bart penalises.  `--tv-time`, `--basis` and `--toeplitz` with M > 1 are refused
+(maps inside frames is not the column order GradientT and FrameBasis act on; ToeplitzNormal takes one set).  No flag: the file
+carries M, and `--crop "MAPS:1"` reproduces the run on a file that holds only the first set, bit for bit.  With M = 1 (with or
+without a MAPS axis) the driver builds the trees it built before.
+
 Containers: HDF5 (`.h5`, the reference's format; needs h5py, which this image does not ship) or NumPy `.npz` with
 the same three arrays in the same orientation; the result goes back into the HDF5 file as dataset `rec`, or next to
 an `.npz` input as `<name>.rec.npy`.
@@ -109,12 +127,14 @@ class dim:
 
 
 def parse(argv):
-    ap = argparse.ArgumentParser(prog="indigo_amd.pics", description="Parallel Imaging and Compressed Sensing (non-Cartesian SENSE: CG, L1-wavelet or locally-low-rank FISTA, or total-variation primal-dual).")
+    ap = argparse.ArgumentParser(prog="indigo_amd.pics", description="Parallel Imaging and Compressed Sensing (non-Cartesian SENSE: CG, L1-wavelet or locally-low-rank FISTA, or total-variation primal-dual). "
+                                 "Maps with a MAPS axis of length M > 1 (two sets from an ESPIRiT calibration) are reconstructed as soft-SENSE: M images per frame, "
+                                 "result (X, Y, Z, 1, M[, ..., T]); not with --tv-time, --basis or --toeplitz.")
     ap.add_argument('-i', type=int, default=20, help='number of CG iterations')
     ap.add_argument('--backend', type=str, default='hip', choices=['hip'])
     ap.add_argument('--device', type=int, default=0)
     ap.add_argument('--debug', type=int, default=logging.INFO, help='logging level')
-    ap.add_argument('--crop', help='crop data before recon: --crop "COIL:2,TIME:4"')
+    ap.add_argument('--crop', help='crop data before recon: --crop "COIL:2,TIME:4" (MAPS:1 keeps the first of several sets of maps)')
     ap.add_argument('--lamda', type=float, default=0, help='Tikhonov regularisation parameter')
     ap.add_argument('-O', '--recipe', type=int, default=3, choices=range(5), help='optimization level (pics.py -O)')
     ap.add_argument('--osf', type=float, default=640 / 480, help='gridding oversampling factor (pics.py: 640/480)')
@@ -135,7 +155,7 @@ def parse(argv):
     ap.add_argument('--basis', default=None, help='temporal basis, a .npy file with a T x K array: reconstruct the K coefficient images of the subspace')
     ap.add_argument('--basis-rank', type=int, default=None, help='keep the first K columns of --basis')
     ap.add_argument('--toeplitz', action='store_true', help='evaluate A^H A as one Toeplitz operator on the grid of twice the image size (with --basis: K x K point-spread functions, the cost no longer grows with the frames)')
-    ap.add_argument('data', nargs='?', default="scan.h5", help='k-space data: HDF5 (data/maps/traj) or .npz')
+    ap.add_argument('data', nargs='?', default="scan.h5", help='k-space data: HDF5 (data/maps/traj) or .npz; maps may hold M <= 4 sets on the MAPS axis (soft-SENSE)')
     args = ap.parse_args(argv)
     if args.llr > 0 and args.l1 > 0:
         ap.error("--llr and --l1 cannot be combined: two non-smooth terms in one prox slot are not a prox")
@@ -445,28 +465,50 @@ def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', le
 def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, width=3, fuse=True,
                 l1=0.0, wavelet='db2', levels=3, power_iters=15, step=None, tv=0.0, tv_sigma=None, tv_time=0.0,
                 llr=0.0, llr_block=8, llr_shifts=False, llr_seed=0, basis=None, basis_rank=None, toeplitz=False):
-    """ksp: (1, readout, views, C, 1, ..., T), mps: (X, Y, Z, C, 1), traj: (3, readout, views[, 1, ..., T]) in pixels -> image
-    (X, Y, Z, 1, ..., T).  T > 1 time frames: the block-diagonal problem of the module docstring, one A_t per frame.
+    """ksp: (1, readout, views, C, 1, ..., T), mps: (X, Y, Z, C, M), traj: (3, readout, views[, 1, ..., T]) in pixels -> image
+    (X, Y, Z, 1, M, ..., T).  T > 1 time frames: the block-diagonal problem of the module docstring, one A_t per frame.
+    M > 1 sets of maps: soft-SENSE, M images per frame (module docstring); not with tv_time, basis or toeplitz.
     tv > 0 (or, with T > 1, tv_time > 0): total-variation regularised by the primal-dual iteration (`tv_solve`; with l1 > 0 the
     wavelet term as well); l1 > 0: L1-wavelet regularised by FISTA (`fista_solve`); llr > 0: the locally low-rank term
     (`llr_term`) in the prox slot of whichever of the two applies, in place of the wavelet term; else CG on the normal equations.
     basis: a T x K array (its first basis_rank columns): the temporal-subspace problem of the module docstring, whose unknowns and
     result are the K coefficient images (X, Y, Z, 1, 1, 1, K); every regulariser then acts on those.
     toeplitz: A^H A of every solver is `operators.ToeplitzNormal` (module docstring); A^H y still comes from the gridding operator"""
-    from indigo_amd.transforms import FuseZpadFFT, Optimize, sense_recipe
+    from indigo_amd.transforms import FuseZpadFFT, Optimize, sense_recipe, soft_sense_tree
     from indigo_amd.transforms import reserve_for
     ksp = np.asarray(ksp, dtype=np.complex64)
     mps = np.asarray(mps, dtype=np.complex64)
     traj = np.array(traj, dtype=np.float64)
     ksp_nc_dims = ksp.shape
+    M = mps.shape[dim.MAPS] if mps.ndim > dim.MAPS else 1          # sets of coil maps: M > 1 is soft-SENSE, M images per frame
+    if ksp.ndim > dim.MAPS and ksp.shape[dim.MAPS] != 1:
+        raise ValueError("data has a MAPS axis of length %d: only the maps carry several sets, the k-space is one measurement "
+                         "(MAPS must be 1 in data)" % ksp.shape[dim.MAPS])
     img_dims = mps.shape[:3] + (1,) + ksp.shape[4:]
+    if M > 1:
+        img_dims = img_dims + (1,) * (dim.MAPS + 1 - len(img_dims))
+        img_dims = img_dims[:dim.MAPS] + (M,) + img_dims[dim.MAPS + 1:]
     log.info('img %s %s', img_dims, ksp.dtype)
-    log.info('mps %s, ksp %s, trj %s', mps.shape, ksp.shape, traj.shape)
+    log.info('mps %s, ksp %s, trj %s, sets of maps %d', mps.shape, ksp.shape, traj.shape, M)
     for i in range(3):                                   # trajectory in units of the field of view (pics.py:69-72)
         traj[i] /= mps.shape[i]
     C = ksp.shape[dim.COIL]
     T = ksp.shape[dim.TIME] if ksp.ndim > dim.TIME else 1
-    assert (mps.shape[dim.MAPS] if mps.ndim > dim.MAPS else 1) == 1, "No support for multiple maps."
+    if M > 1:
+        assert int(np.prod(mps.shape[dim.MAPS + 1:])) == 1, "Of the maps only COIL and MAPS may be longer than 1."
+        # soft-SENSE follow-ups (DESIGN.md §7): the unknown is ordered maps inside frames, which is not what these three take
+        if tv_time > 0:
+            raise ValueError("--tv-time cannot be combined with M = %d sets of maps: GradientT differences neighbouring columns of the "
+                             "unknown, which are then the images of one frame's sets, not neighbouring frames" % M)
+        if basis is not None:
+            raise ValueError("--basis cannot be combined with M = %d sets of maps: FrameBasis mixes the columns of the unknown as "
+                             "frames, and they are then the images of the sets inside every frame" % M)
+        if toeplitz:
+            raise ValueError("--toeplitz cannot be combined with M = %d sets of maps: ToeplitzNormal takes one set" % M)
+        if M > 4:
+            raise ValueError("%d sets of maps, at most 4 are supported (Backend.coil_maps)" % M)
+        if llr > 0 and M * T > 32:
+            raise ValueError("--llr: M * T = %d x %d = %d columns, at most 32 are supported (Backend.llr_threshold)" % (M, T, M * T))
     assert mps.ndim <= dim.TIME or mps.shape[dim.TIME] == 1, "The maps carry no TIME axis: one set for all frames."
     T_traj = traj.shape[dim.TIME] if traj.ndim > dim.TIME else 1
     assert T_traj in (1, T), "traj has %d time frames, data has %d" % (T_traj, T)
@@ -488,7 +530,14 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
 
     def frame_operators(trj3):
         """A_t and A_t^H A_t + lamda I of one trajectory (in a temporal subspace A_t^H A_t alone: lamda acts on the coefficients)"""
-        F1 = B.NUFFT(ksp_nc_dims[:3], mps.shape[:3], trj3, width=width, oversamp=(osf, osf, osf), dtype=ksp.dtype)
+        def nufft():
+            return B.NUFFT(ksp_nc_dims[:3], mps.shape[:3], trj3, width=width, oversamp=(osf, osf, osf), dtype=ksp.dtype)
+        if M > 1:
+            A = soft_sense_tree(B, nufft, mps.reshape(mps.shape[:3] + (C, M)), recipe)
+            AHA = (A.H * A) + lamda * B.Eye(A.shape[1])
+            AHA._name = 'SENSE'
+            return A, AHA
+        F1 = nufft()
         F = B.KronI(C, F1)
         S = B.VStack([B.Diag(mps[:, :, :, c].reshape(mps.shape[:3] + (1,))) for c in range(C)], name='maps')
         A = F * S
@@ -550,7 +599,7 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
     if tv_time > 0 and T == 1:
         log.info("--tv-time %g has no effect on a scan with one time frame", tv_time)
         tv_time = 0.0
-    cols = T if phi is None else K                       # the images of the unknown: the frames, or the coefficient images
+    cols = M * T if phi is None else K                   # the images of the unknown: the sets' images of every frame, or the coefficient images
     term = None
     if llr > 0:
         assert not l1 > 0, "--llr and --l1 cannot be combined: two non-smooth terms in one prox slot are not a prox"

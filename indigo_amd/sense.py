@@ -344,6 +344,28 @@ class SenseProblem(object):
         self.last_support_fine = getattr(A, '_support_fine', None)       # (table, tile) when the tree took a finer table
         return A
 
+    def build_zpadfft_maps(self, backend, maps, **kwargs):
+        """The soft-SENSE tree  A = KronI(C, G') * ZpadFFTMaps  for `maps` = N + (C, M), M sets of coil maps: the
+        tree `build_zpadfft` makes of this problem's trajectory with UNIT maps, whose leaves `transforms.AttachCoilMaps` replaces;
+        shape (C * samples, N * M), the M images stacked map-major.  This problem's own maps are not used, its cached gridding
+        matrices are.  kwargs: `build_zpadfft`'s.  A grid that the leaf takes only behind an image permutation is refused: such
+        scans run through `operators.CoilMaps` (transforms.soft_sense_tree)."""
+        from indigo_amd.transforms import AttachCoilMaps
+        maps = np.asarray(maps, dtype=_C64)
+        assert maps.ndim == 5 and maps.shape[:3] == self.N, (maps.shape, self.N)
+        if fused.image_permutation(backend, self.oN, int(maps.shape[3])) is not None:
+            raise ValueError("build_zpadfft_maps: the fused leaf takes the grid %s only with its image axes permuted" % (self.oN,))
+        ones = np.ones(self.N, dtype=_C64, order='F')
+        q = SenseProblem(self.N, self.coord, lambda c: ones, width=self.width, ntable=self.ntable, oversamp=self.oversamp, ncoils=int(maps.shape[3]))
+        q._interp_cache = self._interp_cache
+        A = q.build_zpadfft(backend, **kwargs)
+        for attr in ('last_support_table', 'last_support_zw', 'last_support_fine'):
+            setattr(self, attr, getattr(q, attr, None))
+        name = A._name
+        A = AttachCoilMaps(maps).visit(A)
+        A._name = name
+        return A
+
     def permuted(self, perm):
         """the same problem with its image axes relabelled (axis a of the new one is axis perm[a] of this one): N, the grid, the
         trajectory rows and the maps permuted (array maps as a transposed view, lazy maps wrapped).  Its gridding matrices live in

@@ -394,6 +394,54 @@ class FuseZpadFFT(Transform):
         return getattr(node, '_fused_layout', 0)
 
 
+class AttachCoilMaps(Transform):
+    """ZpadFFT => ZpadFFTMaps on a fused SENSE tree that was built from UNIT maps: soft-SENSE, M sets of coil maps.
+
+    `maps` is the host array dims + (C, M).  The tree is what `sense_recipe(3) + [FuseZpadFFT]` makes of
+    KronI(C, NUFFT) * VStack(Diag(ones)): every `ZpadFFT` leaf then holds the per-voxel weights of the transform alone (modulation x
+    roll-off x gridding constant) and knows its chunk's coils (`_coil_range`, set by `fused.assemble`).  Each leaf becomes a
+    `ZpadFFTMaps` over its coils of every set, with the same grid, box, layout, support table, support tile and kshift; the parents
+    (`Product`, `HeadRows`, `VStack` over coil chunks) take their widths from their children and so widen to N M columns."""
+
+    def __init__(self, maps):
+        self._maps = np.asarray(maps, dtype=np.complex64)
+        assert self._maps.ndim == 5, "maps must be dims + (coils, sets)"
+
+    def visit_ZpadFFT(self, node):
+        from indigo_amd.operators import ZpadFFTMaps
+        lo, hi = node._coil_range
+        assert node._w_h is not None and node._box == self._maps.shape[:3], "AttachCoilMaps runs on a fresh tree over the maps' own volume"
+        return ZpadFFTMaps(node._backend, node._grid, node._box, node._w_h, self._maps[..., lo:hi, :], hi - lo, box_lo=node._lo,
+                           layout=node._layout, support=node._support_h, support_tile=node._tile_kw.get('support_tile', 16),
+                           kshift=node._tile_kw.get('kshift'), name=node._name)
+
+
+def soft_sense_tree(b, nufft, maps, recipe):
+    """A = KronI(C, F1) * (the map stack of M sets) for the host `maps` = dims + (C, M), F1 = nufft() a fresh single-coil NUFFT, rewritten by
+    `recipe` (`sense_recipe(level)`, with `FuseZpadFFT` at its end for the fused route); shape (C * samples, N M).  Where the recipe
+    fuses the unit-map tree into `ZpadFFT` leaves on the image's own axes, those become `ZpadFFTMaps` (`AttachCoilMaps`).  Else -- no
+    `FuseZpadFFT` in the recipe, a grid the leaf refuses, or one it takes only behind an `AxisPermute` -- the result is the unfused
+    composition Optimize(recipe)(KronI(C, F1)) * CoilMaps(maps)."""
+    from indigo_amd.operators import AxisPermute, ZpadFFT
+    maps = np.asarray(maps, dtype=np.complex64)
+    dims, C = maps.shape[:3], int(maps.shape[3])
+    if FuseZpadFFT in recipe:
+        ones = np.ones(dims + (1,), dtype=np.complex64)
+        S1 = b.VStack([b.Diag(ones) for _ in range(C)], name='maps')
+        A = b.KronI(C, nufft()) * S1
+        A._name = 'SENSE1'
+        A = Optimize(recipe).visit(A)
+        if A.has(ZpadFFT) and not A.has(AxisPermute):
+            A = AttachCoilMaps(maps).visit(A)
+            reserve_for(A, 1)
+            return A
+        log.info("soft-SENSE: the fused leaf does not take this grid on the image's own axes; the maps run as a CoilMaps leaf")
+    A = Optimize([step for step in recipe if step is not FuseZpadFFT]).visit(b.KronI(C, nufft())) * b.CoilMaps(maps, name='maps')
+    A._name = 'SENSE1'
+    reserve_for(A, 1)
+    return A
+
+
 def _permuted_interp(b, gs, grid, perm):
     """the InterpS description of G' on the grid with its axes relabelled by `perm` (trajectory rows, grid and the per-axis phases
     of a separable column scaling permuted) -- or None where there is no description or its column scaling is not separable
