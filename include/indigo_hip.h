@@ -287,6 +287,30 @@ int  ig_psf_mix_c64(ig_ctx* ctx, int64_t n, int64_t nc, int64_t nk, const float*
  * beta != 0.                                                                                                                    */
 int  ig_coil_maps_c64(ig_ctx* ctx, int64_t n, int64_t nc, int64_t nm, const void* maps, int adjoint, const void* x,
                       float alpha_re, float alpha_im, float beta_re, float beta_im, void* y, int64_t ldi, int64_t sg, int64_t sc);
+/* ESPIRiT calibration at image resolution (indigo_amd.ecalib, Backend.place_wrapped, Backend.espirit_eig).  No
+ * reference counterpart.
+ * ig_place_wrapped_c64: vol is a device column-major panel of ncols volumes of n0 x n1 x n2 (first axis fastest), ld >= N = n0 n1 n2 in
+ *   elements; box is a dense device array of ncols boxes of b0 x b1 x b2.  Every element of every volume is written once: zero, or the
+ *   box value: box element (j0, j1, j2) goes to ((j0 - b0/2) mod n0, (j1 - b1/2) mod n1, (j2 - b2/2) mod n2), so the centre element
+ *   b/2 of every axis sits at index 0 and the negative half wraps to the top of the axis.  Values are copied, never computed: bit-exact.
+ *   Rows between the columns are never touched.  A vol that overlaps box is IG_ERR_ARG, with nothing written.  1 <= b_a <= n_a and
+ *   ncols >= 1, else IG_ERR_UNSUPPORTED.  8 bytes per voxel and column, plus the boxes.
+ * ig_espirit_eig_c64: the nm leading eigenpairs of the Hermitian nc x nc matrix G(i) at each of n voxels.  gram is the n x nc(nc+1)/2
+ *   panel (ldg >= n) of the row-wise upper triangle of G, column p nc - p(p-1)/2 + (q - p) holding G[p, q], p <= q; the imaginary
+ *   part of the diagonal is ignored.  maps is the n x (nc nm) panel (ldm >= n): column c + nc m is coil c of set m, so with ldm = n the
+ *   sets are consecutive dense coil-major blocks of n nc elements, the planes ig_coil_maps_c64 takes.  evals is n x nm floats
+ *   (lde >= n).  Eigenvalues descend with m; every vector has unit 2-norm over the coils and is rotated so that its coil-0 component is
+ *   real and >= 0 (a vector whose coil-0 magnitude is below 1e-6 is left unrotated); where eigenvalue m < crop the nc map values of set
+ *   m are exact zeros (evals keeps the eigenvalue).  All arithmetic is float32.  nc <= 8: cyclic Jacobi on the whole matrix, at most
+ *   `iters` sweeps, ended early when no rotation is left (independent of the gaps between eigenvalues).  9 <= nc <= 32: `iters` rounds
+ *   of orthogonal iteration on nm vectors from a fixed start (the error of pair m is of the order (lambda_{nm+1} / lambda_m)^iters).
+ *   Rows between the columns are never touched.  maps or evals overlapping gram or each other is IG_ERR_ARG, with nothing written.
+ *   1 <= nc <= 32, 1 <= nm <= min(4, nc), n >= 1 and 0 <= iters <= 100000, else IG_ERR_UNSUPPORTED.
+ *   One pass: 8 (nc(nc+1)/2 + nc nm) + 4 nm bytes per voxel (424 at 8 coils and 2 sets).                                           */
+int  ig_place_wrapped_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t ncols, int64_t b0, int64_t b1, int64_t b2,
+                          const void* box, void* vol, int64_t ld);
+int  ig_espirit_eig_c64(ig_ctx* ctx, int64_t n, int64_t nc, int64_t nm, int64_t iters, float crop, const void* gram, int64_t ldg,
+                        void* maps, int64_t ldm, float* evals, int64_t lde);
 
 /* ------------------------------------------------------------------------
  * CSR x dense-panel SpMM.  Replaces Backend.ccsrmm

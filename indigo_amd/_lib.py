@@ -91,6 +91,9 @@ PROTOTYPES = {
     "ig_psf_mix_c64":     (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64]),
     "ig_coil_maps_c64":   (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p,
                                    c_float, c_float, c_float, c_float, c_void_p, c_int64, c_int64, c_int64]),
+    "ig_place_wrapped_c64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64]),
+    "ig_espirit_eig_c64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_float, c_void_p, c_int64, c_void_p, c_int64,
+                                   c_void_p, c_int64]),
     "ig_ccsrmm_il":      (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64,
                                    c_float, c_float, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_float, c_float, c_void_p, c_int64]),

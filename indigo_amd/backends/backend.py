@@ -833,6 +833,69 @@ class Backend(object):
             out = out.T if interleaved else out
         y.copy_from(np.asfortranarray(out.astype(_C64).reshape(y.shape, order='F')))
 
+    def place_wrapped(self, vol, box, dims, box_dims):
+        """Zero the columns of the panel `vol` (volumes of `dims`, F-order, one per column) and write column j of `box` (a dense array
+        of boxes of `box_dims`, F-order) into column j with the box's centre element b // 2 of every axis at index 0 and its negative
+        half wrapped to the top of the axis: box element j_a goes to (j_a - b_a // 2) mod n_a.  The input of the inverse transforms
+        that evaluate the ESPIRiT matrices G(x) (indigo_amd.ecalib).  Values are copied: bit-exact.  Rows between
+        the columns of a padded vol are not touched.  1 <= b_a <= n_a.  Host form through to_host / copy_from; device backends
+        override it."""
+        dims, box_dims = tuple(int(n) for n in dims), tuple(int(b) for b in box_dims)
+        N, nb = int(np.prod(dims)), int(np.prod(box_dims))
+        if not all(1 <= b <= n for b, n in zip(box_dims, dims)):
+            raise RuntimeError("place_wrapped: a box of %s in a volume of %s: every side between 1 and the volume's" % (box_dims, dims))
+        ncols = box.size // nb
+        assert ncols >= 1 and box.size == nb * ncols and vol.size == N * ncols, (vol.shape, box.shape, dims, box_dims)
+        b = box.to_host().reshape(box_dims + (ncols,), order='F')
+        out = np.zeros(dims + (ncols,), dtype=b.dtype, order='F')
+        idx = np.ix_(*[(np.arange(bb) - bb // 2) % n for bb, n in zip(box_dims, dims)])
+        out[idx] = b
+        vol.copy_from(np.asfortranarray(out.reshape(vol.shape, order='F')))
+
+    @staticmethod
+    def espirit_unpack(gram, n, C):
+        """the (n, C, C) complex128 Hermitian matrices of an `espirit_eig` panel: column p C - p (p - 1) / 2 + (q - p) holds G[p, q],
+        p <= q (the row-wise upper triangle); the imaginary part of the diagonal is ignored"""
+        g = np.asarray(gram, dtype=np.complex128).reshape((n, C * (C + 1) // 2), order='F')
+        G = np.zeros((n, C, C), dtype=np.complex128)
+        col = 0
+        for p in range(C):
+            for q in range(p, C):
+                if p == q:
+                    G[:, p, p] = g[:, col].real
+                else:
+                    G[:, p, q] = g[:, col]
+                    G[:, q, p] = np.conj(g[:, col])
+                col += 1
+        return G
+
+    def espirit_eig(self, maps, evals, gram, n, ncoils, nmaps, iters=30, crop=0.8):
+        """The M = `nmaps` leading eigenpairs of the Hermitian C x C matrix G at each of `n` voxels, as ESPIRiT maps (indigo_amd.ecalib,
+        DESIGN.md §3.13).  gram is the n x C (C + 1) / 2 panel of the row-wise upper triangle of G (`espirit_unpack`).  maps is the
+        n x (C M) panel, column c + C m coil c of set m -- contiguous, the M dense coil-major planes that `coil_maps` and
+        operators.CoilMaps take --, evals the n x M float32 panel.  Eigenvalues descend with m; every vector has unit 2-norm over the
+        coils and is rotated so that its coil-0 component is real and >= 0 (left unrotated where its coil-0 magnitude is below 1e-6);
+        where eigenvalue m < crop the map values of set m are zero (evals keeps the eigenvalue).  `iters` bounds the iterations of an
+        iterative method.  1 <= M <= min(4, C), C <= 32.  Host form: numpy.linalg.eigh in complex128 through to_host / copy_from
+        (`iters` is not used); device backends override it."""
+        n, C, M = int(n), int(ncoils), int(nmaps)
+        if not 1 <= C <= 32:
+            raise RuntimeError("espirit_eig: %d coils, between 1 and 32 are supported" % C)
+        if not 1 <= M <= min(4, C):
+            raise RuntimeError("espirit_eig: %d sets of maps from %d coils, between 1 and min(4, coils) are supported" % (M, C))
+        assert n >= 1 and gram.size == n * C * (C + 1) // 2 and maps.size == n * C * M and evals.size == n * M, (gram.shape, maps.shape, evals.shape)
+        G = self.espirit_unpack(gram.to_host(), n, C)
+        lam, vec = np.linalg.eigh(G)
+        lam, vec = lam[:, ::-1][:, :M], vec[:, :, ::-1][:, :, :M]                    # (n, M), (n, C, M), descending
+        v0 = vec[:, 0, :]
+        a0 = np.abs(v0)
+        rot = np.where(a0 >= 1e-6, np.conj(v0) / np.where(a0 >= 1e-6, a0, 1), 1)
+        vec = vec * rot[:, None, :]
+        vec[:, 0, :] = np.where(a0 >= 1e-6, a0, v0)
+        vec = np.where((lam < crop)[:, None, :], 0, vec)
+        maps.copy_from(np.asfortranarray(vec.astype(_C64).reshape(maps.shape, order='F')))
+        evals.copy_from(np.asfortranarray(lam.astype(np.float32).reshape(evals.shape, order='F')))
+
     @staticmethod
     def psf_unpack(kern, n, K):
         """the (n, K, K) complex128 Hermitian matrices of a `psf_mix` kernel array: K^2 planes of n floats, the K real diagonals,

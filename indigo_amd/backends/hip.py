@@ -935,6 +935,26 @@ class HipBackend(Backend):
         self._check(self._L.ig_coil_maps_c64(self._ctx, n, C, M, ctypes.c_void_p(maps._arr), int(bool(adjoint)), xp, ar, ai, br, bi,
                                              yp, ldi, sg, sc), "ig_coil_maps_c64")
 
+    def place_wrapped(self, vol, box, dims, box_dims):
+        """Backend.place_wrapped on the device (ig_place_wrapped_c64): the volumes are the columns of a panel with its leading
+        dimension, or stacked in one column; the boxes are one dense array"""
+        assert vol.dtype == _C64 and box.dtype == _C64, "only complex64 is supported"
+        dims, box_dims = tuple(int(n) for n in dims), tuple(int(b) for b in box_dims)
+        N, nb = int(np.prod(dims)), int(np.prod(box_dims))
+        ncols = box.size // max(nb, 1)
+        assert box.contiguous and box.size == nb * ncols, (box.shape, box_dims)
+        vp, ld = self._frame_panel(vol, N, ncols)
+        self._check(self._L.ig_place_wrapped_c64(self._ctx, *dims, ncols, *box_dims, ctypes.c_void_p(box._arr), vp, ld), "ig_place_wrapped_c64")
+
+    def espirit_eig(self, maps, evals, gram, n, ncoils, nmaps, iters=30, crop=0.8):
+        """Backend.espirit_eig on the device (ig_espirit_eig_c64): the three panels with their leading dimensions, or stacked in one column"""
+        assert gram.dtype == _C64 and maps.dtype == _C64 and evals.dtype == np.dtype('float32'), "complex64 panels and float32 eigenvalues"
+        n, C, M = int(n), int(ncoils), int(nmaps)
+        (gp, ldg), (mp, ldm), (ep, lde) = (self._frame_panel(gram, n, C * (C + 1) // 2), self._frame_panel(maps, n, C * M),
+                                           self._frame_panel(evals, n, M))
+        self._check(self._L.ig_espirit_eig_c64(self._ctx, n, C, M, int(iters), ctypes.c_float(float(crop)), gp, ldg, mp, ldm, ep, lde),
+                    "ig_espirit_eig_c64")
+
     def psf_mix(self, y, x, kern, n, ncoils, interleaved=False, width=None):
         """Backend.psf_mix on the device (ig_psf_mix_c64): the K images are the columns of panels with their leading
         dimensions, or stacked in one column; y may be x"""

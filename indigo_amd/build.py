@@ -19,7 +19,7 @@ OBJDIR = os.path.join(HERE, "lib", "obj")
 LIBNAME = "libindigo_hip.so"
 
 SOURCES = ["ig_fft_abd0.hip", "ig_fft_abd1.hip", "ig_fft_abd2.hip", "ig_fft_abd3.hip", "ig_fft.hip", "ig_spmm.hip", "ig_gridsep.hip", "ig_context.hip", "ig_blas.hip",
-           "ig_permute.hip", "ig_wavelet.hip", "ig_tv.hip", "ig_llr.hip", "ig_basis.hip", "ig_toep.hip", "ig_maps.hip", "ig_comm.hip", "ig_interp.hip", "ig_dense.hip"]       # (the slow ones first: four compile side by side)
+           "ig_permute.hip", "ig_wavelet.hip", "ig_tv.hip", "ig_llr.hip", "ig_basis.hip", "ig_toep.hip", "ig_maps.hip", "ig_espirit.hip", "ig_comm.hip", "ig_interp.hip", "ig_dense.hip"]       # (the slow ones first: four compile side by side)
 ARCH = "gfx950"
 CXXFLAGS = [
     "--offload-arch=%s" % ARCH, "-O3", "-std=c++17", "-fPIC",
@@ -36,6 +36,9 @@ EXTRA_FLAGS = {
     "ig_fft.hip": os.environ.get("INDIGO_FFT_FLAGS", "-fno-slp-vectorize").split(),
     "ig_fft_abd0.hip": ["-fno-slp-vectorize"], "ig_fft_abd1.hip": ["-fno-slp-vectorize"],
     "ig_fft_abd2.hip": ["-fno-slp-vectorize"], "ig_fft_abd3.hip": ["-fno-slp-vectorize"],
+    # the SLP vectoriser turns the complex products into v_pk_fma_f32 and keeps a negated and swapped copy of every loop-invariant
+    # matrix element for them: k_esp_orth held 3 x its 128 matrix registers and spilled (up to 1.4 KB of scratch per lane)
+    "ig_espirit.hip": ["-fno-slp-vectorize"],
     # host-only double-precision arithmetic that must round like the reference's (numpy / numba): no fused multiply-add
     "ig_interp.hip": ["-ffp-contract=off"],
 }

@@ -10,6 +10,7 @@ total-variation primal-dual; time frames one by one or in a temporal subspace; s
     python -m indigo_amd.pics --basis PHI.npy [--basis-rank K] [--l1 LAMBDA | --llr LAMBDA] [--tv MU] ... frames.npz
     python -m indigo_amd.pics --toeplitz [--basis PHI.npy ...] ... scan.npz | frames.npz        (A^H A as one Toeplitz operator)
     python -m indigo_amd.pics [--l1 | --tv | --llr ...] [--crop "MAPS:1"] espirit.npz           (maps with a MAPS axis of length M: soft-SENSE)
+    python -m indigo_amd.pics --maps scan.maps.npy ... scan.npz                                  (maps from python -m indigo_amd.ecalib scan.npz)
 
 The counterpart of the reference's driver script (examples/pics.py:20-95 arguments, data layout and tree
 construction, :179-233 recipe, normal equations, CG, output): reads `data` (k-space), `maps` (coil sensitivities)
@@ -103,6 +104,10 @@ voxels) x (M T) matrices (M T <= 32), which is what bart penalises.  `--tv-time`
 carries M, and `--crop "MAPS:1"` reproduces the run on a file that holds only the first set, bit for bit.  With M = 1 (with or
 without a MAPS axis) the driver builds the trees it built before.
 
+Maps from a file.  `--maps FILE.npy` takes the coil maps from that file, (X, Y, Z, C, M) stored reversed -- what
+`python -m indigo_amd.ecalib` estimates from the scan's own k-space centre --, in place of the scan's `maps`; the scan
+then need not hold any.  The M of the file selects SENSE or soft-SENSE as above.  Without the flag nothing changes.
+
 Containers: HDF5 (`.h5`, the reference's format; needs h5py, which this image does not ship) or NumPy `.npz` with
 the same three arrays in the same orientation; the result goes back into the HDF5 file as dataset `rec`, or next to
 an `.npz` input as `<name>.rec.npy`.
@@ -155,6 +160,7 @@ def parse(argv):
     ap.add_argument('--basis', default=None, help='temporal basis, a .npy file with a T x K array: reconstruct the K coefficient images of the subspace')
     ap.add_argument('--basis-rank', type=int, default=None, help='keep the first K columns of --basis')
     ap.add_argument('--toeplitz', action='store_true', help='evaluate A^H A as one Toeplitz operator on the grid of twice the image size (with --basis: K x K point-spread functions, the cost no longer grows with the frames)')
+    ap.add_argument('--maps', default=None, help='coil maps from this .npy file, (X, Y, Z, C, M) stored reversed (what python -m indigo_amd.ecalib writes), in place of the scan\'s `maps`')
     ap.add_argument('data', nargs='?', default="scan.h5", help='k-space data: HDF5 (data/maps/traj) or .npz; maps may hold M <= 4 sets on the MAPS axis (soft-SENSE)')
     args = ap.parse_args(argv)
     if args.llr > 0 and args.l1 > 0:
@@ -174,12 +180,19 @@ def parse(argv):
     return args
 
 
-def load(path):
-    """-> (data, maps, traj, writer): arrays as stored (reversed dimension order), writer(img_T) stores `rec`"""
+def load(path, maps_file=None):
+    """-> (data, maps, traj, writer): arrays as stored (reversed dimension order), writer(img_T) stores `rec`.  maps_file: a .npy
+    file whose array takes the place of the scan's `maps`, which the scan then need not hold (`--maps`)"""
     if path.endswith(".npz"):
         z = np.load(path)
         out = os.path.splitext(path)[0] + ".rec.npy"
-        return z['data'], z['maps'], z['traj'], lambda rec: np.save(out, rec)
+        if maps_file is not None:
+            maps = np.load(maps_file)
+        elif 'maps' in z:
+            maps = z['maps']
+        else:
+            raise ValueError("pics: %s holds no `maps`: give --maps FILE.npy (python -m indigo_amd.ecalib writes one from the scan itself)" % path)
+        return z['data'], maps, z['traj'], lambda rec: np.save(out, rec)
     try:
         import h5py
     except ImportError:
@@ -191,7 +204,9 @@ def load(path):
             del hdf['rec']
         hdf.create_dataset('rec', data=rec)
         hdf.close()
-    return hdf['data'][:], hdf['maps'][:], hdf['traj'][:], write
+    if maps_file is None and 'maps' not in hdf:
+        raise ValueError("pics: %s holds no `maps`: give --maps FILE.npy (python -m indigo_amd.ecalib writes one from the scan itself)" % path)
+    return hdf['data'][:], (np.load(maps_file) if maps_file is not None else hdf['maps'][:]), hdf['traj'][:], write
 
 
 def crop_limits(spec):
@@ -629,7 +644,7 @@ def main(argv=None, backend=None):
         from indigo_amd.backends import get_backend
         backend = get_backend(args.backend, device_id=args.device)
     log.info("using backend: %s", type(backend).__name__)
-    data, maps, traj, write = load(args.data)
+    data, maps, traj, write = load(args.data, args.maps)
     basis = np.load(args.basis) if args.basis is not None else None
     crops = crop_limits(args.crop)
     ksp = data[tuple(slice(0, min(n, c)) for n, c in zip(data.shape, crops[-data.ndim:]))].T
