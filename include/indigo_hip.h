@@ -311,6 +311,18 @@ int  ig_place_wrapped_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64
                           const void* box, void* vol, int64_t ld);
 int  ig_espirit_eig_c64(ig_ctx* ctx, int64_t n, int64_t nc, int64_t nm, int64_t iters, float crop, const void* gram, int64_t ldg,
                         void* maps, int64_t ldm, float* evals, int64_t lde);
+/* The coil Gram matrix of coil compression and noise prewhitening (indigo_amd.cc, Backend.coil_gram).  No reference
+ * counterpart.  x is a device column-major panel of n samples x nc coils (coil c is column c, ldx >= n in elements):
+ *     G[p, q] = sum_i x[i, p] conj(x[i, q])                                  Hermitian, positive semi-definite
+ * parts is a device column-major panel of ceil(n / slab) rows and nc (nc + 1) / 2 columns (ldp >= the rows): row j holds the sum over
+ * the samples [j slab, min(n, (j + 1) slab)) in the packing ig_espirit_eig_c64 reads, column p nc - p(p-1)/2 + (q - p) holding
+ * [p, q], p <= q.  The imaginary part of a diagonal entry is exactly 0.  The caller adds the rows (in float64).  Deterministic: no
+ * atomics and a fixed summation order, two calls give the same bits; inside a slab a float32 fma chain covers slab / 8 samples
+ * (slab / 4 beyond 32 coils) and the chains are added pairwise.  float32-input MFMA on [Re x | Im x]: exact float32 products, one rounding per product.
+ * Rows of x below n (the padding of a leading dimension) are never read, x is never written, rows of parts below its
+ * ceil(n / slab) are never touched.  A parts that overlaps x is IG_ERR_ARG, with nothing written.  1 <= nc <= 64, n >= 1 and
+ * slab >= 1, else IG_ERR_UNSUPPORTED.  One pass: 8 n nc bytes read, 4 nc^2 n real flops.                                          */
+int  ig_coil_gram_c64(ig_ctx* ctx, int64_t n, int64_t nc, const void* x, int64_t ldx, int64_t slab, void* parts, int64_t ldp);
 
 /* ------------------------------------------------------------------------
  * CSR x dense-panel SpMM.  Replaces Backend.ccsrmm

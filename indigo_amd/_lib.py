@@ -94,7 +94,8 @@ PROTOTYPES = {
     "ig_place_wrapped_c64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64]),
     "ig_espirit_eig_c64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_float, c_void_p, c_int64, c_void_p, c_int64,
                                    c_void_p, c_int64]),
-    "ig_ccsrmm_il":      (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64,
+    "ig_coil_gram_c64":   (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64]),
+    "ig_ccsrmm_il":     (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64,
                                    c_float, c_float, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_float, c_float, c_void_p, c_int64]),
     "ig_ccsrmm_il_rw":    (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64,

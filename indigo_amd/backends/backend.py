@@ -896,6 +896,38 @@ class Backend(object):
         maps.copy_from(np.asfortranarray(vec.astype(_C64).reshape(maps.shape, order='F')))
         evals.copy_from(np.asfortranarray(lam.astype(np.float32).reshape(evals.shape, order='F')))
 
+    def coil_gram(self, x, n, ncoils, slab=None):
+        """G[p, q] = sum_i x[i, p] conj(x[i, q]) over the `n` samples of a coil panel, as a host (C, C) complex128 array: Hermitian,
+        positive semi-definite, the matrix coil compression and noise prewhitening start from (indigo_amd.cc).  x is
+        the n x C panel (coil c is column c, with its leading dimension) or the same as an (n C, 1) vector; it is not written, and
+        rows between the columns of a padded panel are not read.  C <= 64.  `slab`: the samples per partial sum of a device backend
+        (None: its default), without meaning here.  Host form in float64 through to_host -- real products of [Re x | Im x], as the
+        device kernel forms them --; device backends override it."""
+        n, C = int(n), int(ncoils)
+        if not 1 <= C <= 64:
+            raise RuntimeError("coil_gram: %d coils, between 1 and 64 are supported" % C)
+        assert n >= 1 and x.size == n * C, (x.shape, n, C)
+        v = x.to_host().reshape((n, C), order='F')
+        re, im = v.real.astype(np.float64), v.imag.astype(np.float64)
+        ri = im.T @ re
+        G = (re.T @ re + im.T @ im) + 1j * (ri - ri.T)
+        G[np.diag_indices(C)] = G[np.diag_indices(C)].real
+        return G
+
+    def coil_mix(self, y, x, A, n):
+        """y[i, v] = sum_c A[v, c] x[i, c]: the host V x C matrix `A` applied along the coil axis of the n x C panel x, into the
+        n x V panel y (panels with their leading dimensions, or stacked in one column): coil compression and prewhitening of data,
+        maps and calibration blocks (indigo_amd.cc).  No kernel of its own: this is `frame_basis` with
+        phi = A^H (C x V) and adjoint=True, y[i, v] = sum_c conj(phi[c, v]) x[i, c] -- ig_basis_c64 with nt = C, nk = V on the
+        device, whose bound nk <= 32 is the bound on V.  y must not overlap x."""
+        A = np.asarray(A)
+        assert A.ndim == 2, A.shape
+        V, C = A.shape
+        if not 1 <= V <= 32:
+            raise RuntimeError("coil_mix: %d virtual coils, between 1 and 32 are supported (frame_basis)" % V)
+        phi = self.copy_array(np.asfortranarray(A.conj().T.astype(_C64)), name='cc.phi')
+        self.frame_basis(y, x, phi, n, adjoint=True)
+
     @staticmethod
     def psf_unpack(kern, n, K):
         """the (n, K, K) complex128 Hermitian matrices of a `psf_mix` kernel array: K^2 planes of n floats, the K real diagonals,

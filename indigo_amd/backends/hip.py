@@ -71,7 +71,10 @@ class HipBackend(Backend):
         self.tuning = dict(placement_candidates=3, placement_min_bytes=1 << 31, placement_window_gb=24, placement_window_allocs=3, fold_odd_axes=True, real_gridding=True, gather_order=True, cg_graph=False, bricks=(4, 8), slots=(1, 2), slot_shape=(4, 4, 256, 64), support_tile={8: 4, 4: 8}, brick_shape={8: (2, 2, 4096, 4096), 4: (2, 4, 4096, 4096)}, xrows=True, runs=True, wide_bricks=True,
                            wide_brick_shape=(2, 2), wide_task_shape=(8192, 2048),
                            # round 6: gridding from the separable form of the matrix (one record per sample, taps computed)
-                           separable=True, sep_gather=True, sep_scatter=True, shares=(4, 8), shares_min_tw=6, share_shape={8: (4, 4, 128, 1024), 4: (4, 4, 128, 1024)})
+                           separable=True, sep_gather=True, sep_scatter=True, shares=(4, 8), shares_min_tw=6, share_shape={8: (4, 4, 128, 1024), 4: (4, 4, 128, 1024)},
+                           # samples per partial sum of coil_gram: a float32 chain of gram_slab / 8 = 2048 samples per wave (/ 4 beyond 32 coils), 1024 workgroups
+                           # and 17 MB of partial sums at 2^24 samples x 64 coils
+                           gram_slab=16384)
 
     def __del__(self):
         try:
@@ -954,6 +957,26 @@ class HipBackend(Backend):
                                            self._frame_panel(evals, n, M))
         self._check(self._L.ig_espirit_eig_c64(self._ctx, n, C, M, int(iters), ctypes.c_float(float(crop)), gp, ldg, mp, ldm, ep, lde),
                     "ig_espirit_eig_c64")
+
+    def coil_gram_parts(self, x, n, ncoils, slab=None):
+        """the partial Gram matrices of ig_coil_gram_c64 on the host: ceil(n / slab) rows (row j: the samples [j slab, (j + 1) slab))
+        of C (C + 1) / 2 complex64 columns, the row-wise upper triangle (`espirit_unpack`)"""
+        assert x.dtype == _C64, "only complex64 is supported"
+        n, C = int(n), int(ncoils)
+        slab = self.tuning['gram_slab'] if slab is None else int(slab)
+        xp, ldx = self._frame_panel(x, n, C)
+        rows = max(1, -(-n // max(slab, 1)))
+        parts = self.empty_array((rows, C * (C + 1) // 2), _C64, name='cc.parts')
+        self._check(self._L.ig_coil_gram_c64(self._ctx, n, C, xp, ldx, slab, ctypes.c_void_p(parts._arr), parts._leading_dim), "ig_coil_gram_c64")
+        return parts.to_host()
+
+    def coil_gram(self, x, n, ncoils, slab=None):
+        """Backend.coil_gram on the device (ig_coil_gram_c64): one partial sum per slab of `slab` samples (default
+        tuning['gram_slab']), the rows added on the host in float64"""
+        C = int(ncoils)
+        parts = self.coil_gram_parts(x, n, C, slab)
+        total = np.add.reduce(parts, axis=0, dtype=np.complex128)
+        return self.espirit_unpack(total.reshape((1, -1)), 1, C)[0]
 
     def psf_mix(self, y, x, kern, n, ncoils, interleaved=False, width=None):
         """Backend.psf_mix on the device (ig_psf_mix_c64): the K images are the columns of panels with their leading

@@ -11,6 +11,7 @@ total-variation primal-dual; time frames one by one or in a temporal subspace; s
     python -m indigo_amd.pics --toeplitz [--basis PHI.npy ...] ... scan.npz | frames.npz        (A^H A as one Toeplitz operator)
     python -m indigo_amd.pics [--l1 | --tv | --llr ...] [--crop "MAPS:1"] espirit.npz           (maps with a MAPS axis of length M: soft-SENSE)
     python -m indigo_amd.pics --maps scan.maps.npy ... scan.npz                                  (maps from python -m indigo_amd.ecalib scan.npz)
+    python -m indigo_amd.pics --cc V ... scan.npz                                                (V virtual coils: python -m indigo_amd.cc in passing)
 
 The counterpart of the reference's driver script (examples/pics.py:20-95 arguments, data layout and tree
 construction, :179-233 recipe, normal equations, CG, output): reads `data` (k-space), `maps` (coil sensitivities)
@@ -108,6 +109,11 @@ Maps from a file.  `--maps FILE.npy` takes the coil maps from that file, (X, Y, 
 `python -m indigo_amd.ecalib` estimates from the scan's own k-space centre --, in place of the scan's `maps`; the scan
 then need not hold any.  The M of the file selects SENSE or soft-SENSE as above.  Without the flag nothing changes.
 
+Coil compression.  `--cc V` cuts `data` and the maps (the scan's or those of `--maps`), after `--crop`, to V virtual coils before the
+reconstruction sees them: `indigo_amd.cc.compress` with the Gram matrix of all samples of all frames and no whitening (DESIGN.md §3.14;
+`python -m indigo_amd.cc` writes the compressed scan, takes noise samples and a calibration region).  An iteration then costs V / C
+of what it did.  Data and maps with different coil counts are refused.  Without the flag the driver runs the code it ran before.
+
 Containers: HDF5 (`.h5`, the reference's format; needs h5py, which this image does not ship) or NumPy `.npz` with
 the same three arrays in the same orientation; the result goes back into the HDF5 file as dataset `rec`, or next to
 an `.npz` input as `<name>.rec.npy`.
@@ -161,6 +167,7 @@ def parse(argv):
     ap.add_argument('--basis-rank', type=int, default=None, help='keep the first K columns of --basis')
     ap.add_argument('--toeplitz', action='store_true', help='evaluate A^H A as one Toeplitz operator on the grid of twice the image size (with --basis: K x K point-spread functions, the cost no longer grows with the frames)')
     ap.add_argument('--maps', default=None, help='coil maps from this .npy file, (X, Y, Z, C, M) stored reversed (what python -m indigo_amd.ecalib writes), in place of the scan\'s `maps`')
+    ap.add_argument('--cc', type=int, default=None, help='compress the coils of data and maps to this many virtual coils first (indigo_amd.cc: all samples, no whitening)')
     ap.add_argument('data', nargs='?', default="scan.h5", help='k-space data: HDF5 (data/maps/traj) or .npz; maps may hold M <= 4 sets on the MAPS axis (soft-SENSE)')
     args = ap.parse_args(argv)
     if args.llr > 0 and args.l1 > 0:
@@ -650,6 +657,9 @@ def main(argv=None, backend=None):
     ksp = data[tuple(slice(0, min(n, c)) for n, c in zip(data.shape, crops[-data.ndim:]))].T
     mps = maps[tuple(slice(0, min(n, c)) for n, c in zip(maps.shape, crops[-maps.ndim:]))].T
     trj = traj[tuple(slice(0, min(n, c)) for n, c in zip(traj.shape, crops[-traj.ndim:]))].T
+    if args.cc is not None:
+        from indigo_amd import cc
+        ksp, mps = cc.compress(backend, ksp, mps, V=args.cc)[:2]
     img = reconstruct(backend, ksp, mps, trj, iters=args.i, lamda=args.lamda, level=args.recipe, osf=args.osf,
                       width=args.width, fuse=not args.no_fuse, l1=args.l1, wavelet=args.wavelet, levels=args.levels,
                       power_iters=args.power_iters, step=args.step, tv=args.tv, tv_sigma=args.tv_sigma, tv_time=args.tv_time,
