@@ -67,18 +67,22 @@ def dwt_plan(dims, wavelet, levels):
     return passes, tuple(c)
 
 
-def _grad_forward(v):
-    """D v for v of shape dims + (ncols,): shape dims + (3, ncols) -- the F-ordered 3N-row columns of Backend.grad3 -- forward
-    differences, zero at the far face"""
-    out = np.zeros(v.shape[:3] + (3,) + v.shape[3:], dtype=v.dtype)
+def _grad_forward(v, comps=3):
+    """D v for v of shape dims + (ncols,): shape dims + (comps, ncols) -- the F-ordered 3N-row columns of Backend.grad3 -- forward
+    differences, zero at the far face; comps = 4 adds the difference along the columns, the frames of Backend.grad4, zero in
+    the last one"""
+    out = np.zeros(v.shape[:3] + (comps,) + v.shape[3:], dtype=v.dtype)
     out[:-1, :, :, 0] = v[1:] - v[:-1]
     out[:, :-1, :, 1] = v[:, 1:] - v[:, :-1]
     out[:, :, :-1, 2] = v[:, :, 1:] - v[:, :, :-1]
+    if comps == 4:
+        out[:, :, :, 3, :-1] = v[..., 1:] - v[..., :-1]
     return out
 
 
 def _grad_adjoint(t):
-    """D^H t for t of shape dims + (3, ncols): shape dims + (ncols,); t on the far face of its own axis is not read"""
+    """D^H t for t of shape dims + (3, ncols), D4^H t for dims + (4, ncols): shape dims + (ncols,); t on the far face of its own
+    axis, and its fourth component in the last column, is not read"""
     out = np.zeros(t.shape[:3] + t.shape[4:], dtype=t.dtype)
     out[1:] += t[:-1, :, :, 0]
     out[:-1] -= t[:-1, :, :, 0]
@@ -86,6 +90,9 @@ def _grad_adjoint(t):
     out[:, :-1] -= t[:, :-1, :, 1]
     out[:, :, 1:] += t[:, :, :-1, 2]
     out[:, :, :-1] -= t[:, :, :-1, 2]
+    if t.shape[3] == 4:
+        out[..., 1:] += t[:, :, :, 3, :-1]
+        out[..., :-1] -= t[:, :, :, 3, :-1]
     return out
 
 
@@ -661,11 +668,15 @@ class Backend(object):
         n = int(np.prod(dims))
         rows_x, rows_y = (3 * n, n) if adjoint else (n, 3 * n)
         assert x.size % rows_x == 0 and x.size // rows_x * rows_y == y.size, (x.shape, y.shape, dims)
-        ncols = x.size // rows_x
+        self._grad_host(y, x, dims, 3, x.size // rows_x, adjoint, alpha, beta)
+
+    def _grad_host(self, y, x, dims, comps, ncols, adjoint, alpha, beta):
+        """`grad3` (comps = 3) and `grad4` (comps = 4: the ncols columns are the frames) in float64"""
+        rows_y = y.size // ncols
         if adjoint:
-            out = _grad_adjoint(x.to_host().reshape(dims + (3, ncols), order='F').astype(np.complex128))
+            out = _grad_adjoint(x.to_host().reshape(dims + (comps, ncols), order='F').astype(np.complex128))
         else:
-            out = _grad_forward(x.to_host().reshape(dims + (ncols,), order='F').astype(np.complex128))
+            out = _grad_forward(x.to_host().reshape(dims + (ncols,), order='F').astype(np.complex128), comps)
         out = out.reshape((rows_y, ncols), order='F') * complex(alpha)
         if beta != 0:
             out = out + complex(beta) * y.to_host().reshape((rows_y, ncols), order='F')
@@ -678,14 +689,23 @@ class Backend(object):
         dims = tuple(int(n) for n in dims)
         n = int(np.prod(dims))
         assert xn.size % n == 0 and xn.size == xo.size and u.size == 3 * xn.size and mu >= 0, (u.shape, xn.shape, xo.shape, dims, mu)
-        ncols = xn.size // n
+        self._tv_dual_host(u, xn, xo, sigma, (mu,), dims, xn.size // n)
+
+    def _tv_dual_host(self, u, xn, xo, sigma, radii, dims, ncols):
+        """`tv_dual_step` (radii = (mu,)) and `tv4_dual_step` (radii = (mu, mu_t): the ncols columns are the frames) in float64"""
+        comps = 2 + len(radii)
         w = 2.0 * xn.to_host().astype(np.complex128) - xo.to_host().astype(np.complex128)
-        t = u.to_host().reshape(dims + (3, ncols), order='F').astype(np.complex128)
-        t = t + float(sigma) * _grad_forward(w.reshape(dims + (ncols,), order='F'))
-        r = np.sqrt((t.real ** 2 + t.imag ** 2).sum(axis=3, keepdims=True))
+        g = float(sigma) * _grad_forward(w.reshape(dims + (ncols,), order='F'), comps)
+        t = u.to_host().reshape(dims + (comps, ncols), order='F').astype(np.complex128)
+        t[:, :, :, :3] += g[:, :, :, :3]
+        r = np.sqrt((t.real ** 2 + t.imag ** 2)[:, :, :, :3].sum(axis=3, keepdims=True))
         with np.errstate(divide='ignore', invalid='ignore'):
-            f = np.where(r <= float(mu), 1.0, float(mu) / r)
-        u.copy_from(np.asfortranarray((t * f).astype(_C64).reshape(u.shape, order='F')))
+            t[:, :, :, :3] *= np.where(r <= float(radii[0]), 1.0, float(radii[0]) / r)
+            if comps == 4:
+                t[:, :, :, 3, :-1] += g[:, :, :, 3, :-1]
+                rt = np.abs(t[:, :, :, 3])
+                t[:, :, :, 3] *= np.where(rt <= float(radii[1]), 1.0, float(radii[1]) / rt)
+        u.copy_from(np.asfortranarray(t.astype(_C64).reshape(u.shape, order='F')))
 
     def grad4(self, y, x, dims, frames, adjoint=False, alpha=1, beta=0):
         """y = beta*y + alpha * D4 x (adjoint: D4^H x) for T = `frames` time frames of an F-ordered `dims` volume of N voxels.  x is
@@ -698,20 +718,7 @@ class Backend(object):
         n, T = int(np.prod(dims)), int(frames)
         rows_x, rows_y = (4 * n, n) if adjoint else (n, 4 * n)
         assert T >= 1 and x.size == rows_x * T and y.size == rows_y * T, (x.shape, y.shape, dims, frames)
-        if adjoint:
-            t = x.to_host().reshape(dims + (4, T), order='F').astype(np.complex128)
-            out = _grad_adjoint(t[:, :, :, :3])
-            out[..., 1:] += t[:, :, :, 3, :-1]
-            out[..., :-1] -= t[:, :, :, 3, :-1]
-        else:
-            v = x.to_host().reshape(dims + (T,), order='F').astype(np.complex128)
-            out = np.zeros(dims + (4, T), dtype=np.complex128)
-            out[:, :, :, :3] = _grad_forward(v)
-            out[:, :, :, 3, :-1] = v[..., 1:] - v[..., :-1]
-        out = out.reshape((rows_y, T), order='F') * complex(alpha)
-        if beta != 0:
-            out = out + complex(beta) * y.to_host().reshape((rows_y, T), order='F')
-        y.copy_from(np.asfortranarray(out.astype(_C64).reshape(y.shape, order='F')))
+        self._grad_host(y, x, dims, 4, T, adjoint, alpha, beta)
 
     def tv4_dual_step(self, u, xn, xo, sigma, mu, mu_t, dims, frames):
         """u <- proj(u + sigma * D4(2*xn - xo)) in place: the dual step of spatial plus temporal total variation on `frames` time
@@ -722,17 +729,7 @@ class Backend(object):
         n, T = int(np.prod(dims)), int(frames)
         assert T >= 1 and xn.size == n * T and xo.size == n * T and u.size == 4 * n * T and mu >= 0 and mu_t >= 0, \
             (u.shape, xn.shape, xo.shape, dims, frames, mu, mu_t)
-        w = 2.0 * xn.to_host().astype(np.complex128) - xo.to_host().astype(np.complex128)
-        w = w.reshape(dims + (T,), order='F')
-        t = u.to_host().reshape(dims + (4, T), order='F').astype(np.complex128)
-        t[:, :, :, :3] += float(sigma) * _grad_forward(w)
-        t[:, :, :, 3, :-1] += float(sigma) * (w[..., 1:] - w[..., :-1])
-        r = np.sqrt((t.real ** 2 + t.imag ** 2)[:, :, :, :3].sum(axis=3, keepdims=True))
-        rt = np.abs(t[:, :, :, 3:])
-        with np.errstate(divide='ignore', invalid='ignore'):
-            t[:, :, :, :3] *= np.where(r <= float(mu), 1.0, float(mu) / r)
-            t[:, :, :, 3:] *= np.where(rt <= float(mu_t), 1.0, float(mu_t) / rt)
-        u.copy_from(np.asfortranarray(t.astype(_C64).reshape(u.shape, order='F')))
+        self._tv_dual_host(u, xn, xo, sigma, (mu, mu_t), dims, T)
 
     @staticmethod
     def _llr_block_ids(dims, block, shift):

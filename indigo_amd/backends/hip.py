@@ -821,31 +821,6 @@ class HipBackend(Backend):
         self._check(self._L.ig_csoft_c64(self._ctx, n0, n1, n2, c0, c1, c2, ncols, ctypes.c_float(float(tau)),
                                          ctypes.c_void_p(x._arr), x._leading_dim), "ig_csoft_c64")
 
-    def grad3(self, y, x, dims, adjoint=False, alpha=1, beta=0):
-        """Backend.grad3 on the device (ig_grad3_c64 / ig_grad3h_c64): panels of any column count with their leading dimensions"""
-        assert x.dtype == _C64 and y.dtype == _C64, "only complex64 is supported"
-        n0, n1, n2 = (int(n) for n in dims)
-        n = n0 * n1 * n2
-        rows_x, rows_y = (3 * n, n) if adjoint else (n, 3 * n)
-        assert x.shape[0] == rows_x and y.shape[0] == rows_y and x.size // rows_x == y.size // rows_y, (x.shape, y.shape, dims)
-        ncols = x.shape[1] if x.ndim == 2 else 1
-        ar, ai = _cplx(alpha)
-        br, bi = _cplx(beta)
-        name = "ig_grad3h_c64" if adjoint else "ig_grad3_c64"
-        self._check(getattr(self._L, name)(self._ctx, n0, n1, n2, ncols, ctypes.c_void_p(x._arr), x._leading_dim, ar, ai, br, bi,
-                                           ctypes.c_void_p(y._arr), y._leading_dim), name)
-
-    def tv_dual_step(self, u, xn, xo, sigma, mu, dims):
-        """Backend.tv_dual_step on the device (ig_tv_dual_c64), in place on u"""
-        assert u.dtype == _C64 and xn.dtype == _C64 and xo.dtype == _C64, "only complex64 is supported"
-        n0, n1, n2 = (int(n) for n in dims)
-        n = n0 * n1 * n2
-        assert xn.shape[0] == n and xo.shape == xn.shape and u.shape[0] == 3 * n and u.size == 3 * xn.size, (u.shape, xn.shape, xo.shape, dims)
-        ncols = xn.shape[1] if xn.ndim == 2 else 1
-        self._check(self._L.ig_tv_dual_c64(self._ctx, n0, n1, n2, ncols, ctypes.c_void_p(xn._arr), xn._leading_dim,
-                                           ctypes.c_void_p(xo._arr), xo._leading_dim, ctypes.c_float(float(sigma)),
-                                           ctypes.c_float(float(mu)), ctypes.c_void_p(u._arr), u._leading_dim), "ig_tv_dual_c64")
-
     @staticmethod
     def _frame_panel(a, rows, frames):
         """(pointer, leading dimension) of `a` as a rows x frames panel: a is that panel, or the (rows * frames, 1) vector"""
@@ -854,28 +829,45 @@ class HipBackend(Backend):
         assert a.shape in ((rows * frames, 1), (rows * frames,)), (a.shape, rows, frames)
         return ctypes.c_void_p(a._arr), rows
 
+    def _grad(self, y, x, dims, comps, ncols, adjoint, alpha, beta):
+        """ig_grad3[h]_c64 (comps = 3) and ig_grad4[h]_c64 (comps = 4) on x and y as panels of ncols columns"""
+        assert x.dtype == _C64 and y.dtype == _C64, "only complex64 is supported"
+        n0, n1, n2 = (int(n) for n in dims)
+        n = n0 * n1 * n2
+        rows_x, rows_y = (comps * n, n) if adjoint else (n, comps * n)
+        (xp, ldx), (yp, ldy) = self._frame_panel(x, rows_x, ncols), self._frame_panel(y, rows_y, ncols)
+        ar, ai = _cplx(alpha)
+        br, bi = _cplx(beta)
+        name = "ig_grad%d%s_c64" % (comps, "h" if adjoint else "")
+        self._check(getattr(self._L, name)(self._ctx, n0, n1, n2, ncols, xp, ldx, ar, ai, br, bi, yp, ldy), name)
+
+    def _tv_dual(self, u, xn, xo, sigma, radii, dims, ncols):
+        """ig_tv_dual_c64 (radii = (mu,)) and ig_tv4_dual_c64 (radii = (mu, mu_t)) on xn, xo and u as panels of ncols columns"""
+        assert u.dtype == _C64 and xn.dtype == _C64 and xo.dtype == _C64, "only complex64 is supported"
+        n0, n1, n2 = (int(n) for n in dims)
+        n = n0 * n1 * n2
+        (np_, ldn), (op_, ldo), (up, ldu) = (self._frame_panel(xn, n, ncols), self._frame_panel(xo, n, ncols),
+                                             self._frame_panel(u, (2 + len(radii)) * n, ncols))
+        name = "ig_tv_dual_c64" if len(radii) == 1 else "ig_tv4_dual_c64"
+        self._check(getattr(self._L, name)(self._ctx, n0, n1, n2, ncols, np_, ldn, op_, ldo, ctypes.c_float(float(sigma)),
+                                           *(ctypes.c_float(float(r)) for r in radii), up, ldu), name)
+
+    def grad3(self, y, x, dims, adjoint=False, alpha=1, beta=0):
+        """Backend.grad3 on the device (ig_grad3_c64 / ig_grad3h_c64): panels of any column count with their leading dimensions"""
+        self._grad(y, x, dims, 3, x.shape[1] if x.ndim == 2 else 1, adjoint, alpha, beta)
+
+    def tv_dual_step(self, u, xn, xo, sigma, mu, dims):
+        """Backend.tv_dual_step on the device (ig_tv_dual_c64), in place on u"""
+        self._tv_dual(u, xn, xo, sigma, (mu,), dims, xn.shape[1] if xn.ndim == 2 else 1)
+
     def grad4(self, y, x, dims, frames, adjoint=False, alpha=1, beta=0):
         """Backend.grad4 on the device (ig_grad4_c64 / ig_grad4h_c64): the frames are the columns of a panel with its leading
         dimension, or stacked in one column"""
-        assert x.dtype == _C64 and y.dtype == _C64, "only complex64 is supported"
-        n0, n1, n2 = (int(n) for n in dims)
-        n, T = n0 * n1 * n2, int(frames)
-        rows_x, rows_y = (4 * n, n) if adjoint else (n, 4 * n)
-        (xp, ldx), (yp, ldy) = self._frame_panel(x, rows_x, T), self._frame_panel(y, rows_y, T)
-        ar, ai = _cplx(alpha)
-        br, bi = _cplx(beta)
-        name = "ig_grad4h_c64" if adjoint else "ig_grad4_c64"
-        self._check(getattr(self._L, name)(self._ctx, n0, n1, n2, T, xp, ldx, ar, ai, br, bi, yp, ldy), name)
+        self._grad(y, x, dims, 4, int(frames), adjoint, alpha, beta)
 
     def tv4_dual_step(self, u, xn, xo, sigma, mu, mu_t, dims, frames):
         """Backend.tv4_dual_step on the device (ig_tv4_dual_c64), in place on u"""
-        assert u.dtype == _C64 and xn.dtype == _C64 and xo.dtype == _C64, "only complex64 is supported"
-        n0, n1, n2 = (int(n) for n in dims)
-        n, T = n0 * n1 * n2, int(frames)
-        (np_, ldn), (op_, ldo), (up, ldu) = (self._frame_panel(xn, n, T), self._frame_panel(xo, n, T),
-                                             self._frame_panel(u, 4 * n, T))
-        self._check(self._L.ig_tv4_dual_c64(self._ctx, n0, n1, n2, T, np_, ldn, op_, ldo, ctypes.c_float(float(sigma)),
-                                            ctypes.c_float(float(mu)), ctypes.c_float(float(mu_t)), up, ldu), "ig_tv4_dual_c64")
+        self._tv_dual(u, xn, xo, sigma, (mu, mu_t), dims, int(frames))
 
     def _llr_args(self, x, dims, frames, block, shift):
         """the leading arguments of ig_llr_svt_c64 / ig_llr_nuc_c64, the panel pointer and its leading dimension, and nb"""

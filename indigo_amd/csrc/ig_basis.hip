@@ -22,22 +22,6 @@ constexpr int BASIS_BLK = 256;
 constexpr int BASIS_LDS = 8192;          // bytes of phi in LDS at a time: 256 rows at NK = 4, 32 rows at NK = 32
 constexpr int64_t BASIS_MAXGRID = 1 << 20;   // workgroups; the voxel loop strides beyond that
 
-// V neighbouring elements of one column: one 8-byte or one 16-byte access
-template <int V>
-__device__ __forceinline__ void ld(float2 (&v)[V], const float2* p) {
-    if constexpr (V == 2) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = make_float2(q.x, q.y); v[1] = make_float2(q.z, q.w);
-    } else {
-        v[0] = *p;
-    }
-}
-template <int V>
-__device__ __forceinline__ void st(float2* p, const float2 (&v)[V]) {
-    if constexpr (V == 2) *reinterpret_cast<float4*>(p) = make_float4(v[0].x, v[0].y, v[1].x, v[1].y);
-    else *p = v[0];
-}
-
 // rows [t0, t0 + tt) of phi into LDS as ph[t][k], zero for the masked tail k >= nk; the caller puts barriers around it
 template <int NK>
 __device__ __forceinline__ void stage_phi(float2 (*ph)[NK], const float2* __restrict__ phi, int64_t ldphi, int64_t t0, int tt, int nk) {
@@ -45,12 +29,6 @@ __device__ __forceinline__ void stage_phi(float2 (*ph)[NK], const float2* __rest
         const int k = e / tt, t = e - k * tt;                               // consecutive threads read consecutive t of a column
         ph[t][k] = k < nk ? phi[t0 + t + (int64_t)k * ldphi] : make_float2(0.f, 0.f);
     }
-}
-
-// acc += conj(p) * a
-__device__ __forceinline__ void cfmac(float2& acc, float2 p, float2 a) {
-    acc.x = fmaf(p.x, a.x, acc.x); acc.x = fmaf(p.y, a.y, acc.x);
-    acc.y = fmaf(p.x, a.y, acc.y); acc.y = fmaf(-p.y, a.x, acc.y);
 }
 
 // nv work items of V voxels each (n = nv * V).  The loops over the workgroup's chunks of voxels and over the staged rows of phi
@@ -70,7 +48,7 @@ k_basis_fwd(int64_t nv, int nk, int64_t nt, const float2* __restrict__ phi, int6
 #pragma unroll
         for (int k = 0; k < NK; ++k, xp += ldx) {
             if (active && k < nk) {
-                ld<V>(xr[k], xp);
+                ldv<V>(xr[k], xp);
 #pragma unroll
                 for (int v = 0; v < V; ++v) xr[k][v] = cmul(a, xr[k][v]);
             } else {
@@ -98,11 +76,11 @@ k_basis_fwd(int64_t nv, int nk, int64_t nt, const float2* __restrict__ phi, int6
                 }
                 if (BETA) {
                     float2 o[V];
-                    ld<V>(o, yp);
+                    ldv<V>(o, yp);
 #pragma unroll
                     for (int v = 0; v < V; ++v) cfma(acc[v], b, o[v]);
                 }
-                st<V>(yp, acc);
+                stv<V>(yp, acc);
             }
         }
     }
@@ -133,7 +111,7 @@ k_basis_adj(int64_t nv, int nk, int64_t nt, const float2* __restrict__ phi, int6
 #pragma unroll UT
             for (int t = 0; t < tt; ++t, xp += ldx) {
                 float2 xv[V];
-                ld<V>(xv, xp);
+                ldv<V>(xv, xp);
 #pragma unroll
                 for (int k = 0; k < NK; ++k) {
                     const float2 p = ph[t][k];
@@ -152,11 +130,11 @@ k_basis_adj(int64_t nv, int nk, int64_t nt, const float2* __restrict__ phi, int6
                 for (int v = 0; v < V; ++v) r[v] = cmul(a, acc[k][v]);
                 if (BETA) {
                     float2 o[V];
-                    ld<V>(o, yp);
+                    ldv<V>(o, yp);
 #pragma unroll
                     for (int v = 0; v < V; ++v) cfma(r[v], b, o[v]);
                 }
-                st<V>(yp, r);
+                stv<V>(yp, r);
             }
         }
     }
@@ -165,19 +143,12 @@ k_basis_adj(int64_t nv, int nk, int64_t nt, const float2* __restrict__ phi, int6
 template <int NK, int V>
 void basis_launch(ig_ctx* ctx, bool adjoint, bool beta, int64_t n, int nk, int64_t nt, const float2* phi, int64_t ldphi,
                   const float2* x, int64_t ldx, float2 a, float2 b, float2* y, int64_t ldy) {
-    const int64_t nv = n / V, blocks = (nv + BASIS_BLK - 1) / BASIS_BLK;
-    const dim3 grid((unsigned)(blocks < BASIS_MAXGRID ? blocks : BASIS_MAXGRID)), block(BASIS_BLK);
+    const int64_t nv = n / V;
+    const dim3 grid = ig_grid_1d(nv, BASIS_BLK, BASIS_MAXGRID), block(BASIS_BLK);
 #define IG_BASIS_GO(KERNEL, BETA) hipLaunchKernelGGL((KERNEL<NK, V, BETA>), grid, block, 0, ctx->stream, nv, nk, nt, phi, ldphi, x, ldx, a, b, y, ldy)
     if (adjoint) { if (beta) IG_BASIS_GO(k_basis_adj, true); else IG_BASIS_GO(k_basis_adj, false); }
     else         { if (beta) IG_BASIS_GO(k_basis_fwd, true); else IG_BASIS_GO(k_basis_fwd, false); }
 #undef IG_BASIS_GO
-}
-
-// whether [p, p + ((cols_p - 1) * ldp + rows) elements) and [q, ...) share a byte
-bool basis_overlap(const void* p, int64_t ldp, int64_t rows_p, int64_t cols_p, const void* q, int64_t ldq, int64_t rows_q, int64_t cols_q) {
-    const uintptr_t p0 = (uintptr_t)p, p1 = p0 + (uintptr_t)((cols_p - 1) * ldp + rows_p) * sizeof(float2);
-    const uintptr_t q0 = (uintptr_t)q, q1 = q0 + (uintptr_t)((cols_q - 1) * ldq + rows_q) * sizeof(float2);
-    return p0 < q1 && q0 < p1;
 }
 
 }  // namespace
@@ -195,8 +166,8 @@ int ig_basis_c64(ig_ctx* ctx, int64_t n, int64_t nk, int64_t nt, const void* phi
     IG_REQUIRE(ctx, ldx >= n && ldy >= n, "ig_basis_c64: leading dimension (%lld, %lld) below n = %lld", (long long)ldx, (long long)ldy, (long long)n);
     IG_REQUIRE(ctx, phi && x && y, "ig_basis_c64: NULL pointer");
     const int64_t cols_x = adjoint ? nt : nk, cols_y = adjoint ? nk : nt;
-    IG_REQUIRE(ctx, !basis_overlap(x, ldx, n, cols_x, y, ldy, n, cols_y), "ig_basis_c64: y overlaps x");
-    IG_REQUIRE(ctx, !basis_overlap(phi, ldphi, nt, nk, y, ldy, n, cols_y), "ig_basis_c64: y overlaps phi");
+    IG_REQUIRE(ctx, !ig_panels_overlap(x, ldx, n, cols_x, y, ldy, n, cols_y), "ig_basis_c64: y overlaps x");
+    IG_REQUIRE(ctx, !ig_panels_overlap(phi, ldphi, nt, nk, y, ldy, n, cols_y), "ig_basis_c64: y overlaps phi");
     if (int rc = ig_set_device(ctx)) return rc;
     const bool beta = !(br == 0.f && bi == 0.f);
     const float2 a = make_float2(ar, ai), b = make_float2(br, bi);

@@ -126,6 +126,45 @@ __device__ __forceinline__ void cfma(float2& acc, float2 a, float2 b) {
     acc.x = fmaf(a.x, b.x, acc.x); acc.x = fmaf(-a.y, b.y, acc.x);
     acc.y = fmaf(a.x, b.y, acc.y); acc.y = fmaf(a.y, b.x, acc.y);
 }
+// acc += conj(p)*q
+__device__ __forceinline__ void cfmac(float2& acc, float2 p, float2 q) {
+    acc.x = fmaf(p.x, q.x, acc.x); acc.x = fmaf(p.y, q.y, acc.x);
+    acc.y = fmaf(p.x, q.y, acc.y); acc.y = fmaf(-p.y, q.x, acc.y);
+}
+
+// V neighbouring elements: one 8-byte or one 16-byte access (V == 2: p is 16-byte aligned)
+template <int V>
+__device__ __forceinline__ void ldv(float2 (&v)[V], const float2* p) {
+    if constexpr (V == 2) {
+        const float4 q = *reinterpret_cast<const float4*>(p);
+        v[0] = make_float2(q.x, q.y); v[1] = make_float2(q.z, q.w);
+    } else {
+        v[0] = *p;
+    }
+}
+template <int V>
+__device__ __forceinline__ void stv(float2* p, const float2 (&v)[V]) {
+    if constexpr (V == 2) *reinterpret_cast<float4*>(p) = make_float4(v[0].x, v[0].y, v[1].x, v[1].y);
+    else *p = v[0];
+}
+
+// ---- argument checks and launch shapes (host) ---------------------------------
+// whether the byte ranges [p0, p1) and [q0, q1) share a byte
+static inline bool ig_bytes_overlap(uintptr_t p0, uintptr_t p1, uintptr_t q0, uintptr_t q1) { return p0 < q1 && q0 < p1; }
+// the same for two column-major complex64 panels: [p, p + ((cols_p - 1) * ldp + rows_p) elements) and [q, ...)
+static inline bool ig_panels_overlap(const void* p, int64_t ldp, int64_t rows_p, int64_t cols_p,
+                                     const void* q, int64_t ldq, int64_t rows_q, int64_t cols_q) {
+    const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
+    return ig_bytes_overlap(p0, p0 + (uintptr_t)((cols_p - 1) * ldp + rows_p) * sizeof(float2),
+                            q0, q0 + (uintptr_t)((cols_q - 1) * ldq + rows_q) * sizeof(float2));
+}
+// v clamped to [1, hi]: a grid extent (the kernels stride over what does not fit)
+static inline int64_t ig_clamp1(int64_t v, int64_t hi) { return v < 1 ? 1 : (v > hi ? hi : v); }
+// workgroups of per_block items for n items, at most max_blocks of them
+static inline dim3 ig_grid_1d(int64_t n, int per_block, int64_t max_blocks) {
+    const int64_t blocks = (n + per_block - 1) / per_block;
+    return dim3((unsigned)(blocks < max_blocks ? blocks : max_blocks));
+}
 
 // Raw buffer accesses: 128-bit descriptor (wave-uniform base, 2 GB window) + per-lane 32-bit byte offset + uniform
 // byte offset.  A lane offset >= the window (IG_OOB) is out of range: loads return 0, stores are dropped.

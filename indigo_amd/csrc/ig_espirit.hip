@@ -300,11 +300,6 @@ k_esp_orth(int64_t n, int nc, int iters, float crop, const float2* __restrict__ 
     }
 }
 
-dim3 esp_grid(int64_t items, int per_block) {
-    const int64_t blocks = (items + per_block - 1) / per_block;
-    return dim3((unsigned)(blocks < ESP_MAXGRID ? blocks : ESP_MAXGRID));
-}
-
 template <int R, int L>
 void esp_launch_orth(ig_ctx* ctx, int64_t n, int nc, int nm, int iters, float crop, const float2* gram, int64_t ldg,
                      float2* maps, int64_t ldm, float* evals, int64_t lde) {
@@ -314,8 +309,6 @@ void esp_launch_orth(ig_ctx* ctx, int64_t n, int nc, int nm, int iters, float cr
     if (nm == 1) IG_ESP_ORTH(1); else if (nm == 2) IG_ESP_ORTH(2); else if (nm == 3) IG_ESP_ORTH(3); else IG_ESP_ORTH(4);
 #undef IG_ESP_ORTH
 }
-
-bool esp_overlap(uintptr_t p0, uintptr_t p1, uintptr_t q0, uintptr_t q1) { return p0 < q1 && q0 < p1; }
 
 }  // namespace
 
@@ -333,10 +326,10 @@ int ig_place_wrapped_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_
     IG_REQUIRE(ctx, box && vol, "ig_place_wrapped_c64: NULL pointer");
     const uintptr_t s0 = (uintptr_t)box, s1 = s0 + (uintptr_t)(nb * ncols) * sizeof(float2);
     const uintptr_t v0 = (uintptr_t)vol, v1 = v0 + (uintptr_t)((ncols - 1) * ld + N) * sizeof(float2);
-    IG_REQUIRE(ctx, !esp_overlap(s0, s1, v0, v1), "ig_place_wrapped_c64: the volumes overlap the boxes");
+    IG_REQUIRE(ctx, !ig_bytes_overlap(s0, s1, v0, v1), "ig_place_wrapped_c64: the volumes overlap the boxes");
     if (int rc = ig_set_device(ctx)) return rc;
     ig_prof_scope prof(ctx, "place_wrapped", 8.0 * (double)ncols * (double)(N + nb));
-    hipLaunchKernelGGL(k_place_wrapped, esp_grid(N * ncols, 256), dim3(256), 0, ctx->stream, n0, n1, n2, ncols, b0, b1, b2,
+    hipLaunchKernelGGL(k_place_wrapped, ig_grid_1d(N * ncols, 256, ESP_MAXGRID), dim3(256), 0, ctx->stream, n0, n1, n2, ncols, b0, b1, b2,
                        (const float2*)box, (float2*)vol, ld);
     IG_LAUNCH_CHECK(ctx, "k_place_wrapped");
     return IG_OK;
@@ -363,16 +356,16 @@ int ig_espirit_eig_c64(ig_ctx* ctx, int64_t n, int64_t nc, int64_t nm, int64_t i
     const uintptr_t g0 = (uintptr_t)gram, g1 = g0 + (uintptr_t)((ntri - 1) * ldg + n) * sizeof(float2);
     const uintptr_t m0 = (uintptr_t)maps, m1 = m0 + (uintptr_t)((nc * nm - 1) * ldm + n) * sizeof(float2);
     const uintptr_t e0 = (uintptr_t)evals, e1 = e0 + (uintptr_t)((nm - 1) * lde + n) * sizeof(float);
-    IG_REQUIRE(ctx, !esp_overlap(g0, g1, m0, m1), "ig_espirit_eig_c64: maps overlaps gram");
-    IG_REQUIRE(ctx, !esp_overlap(g0, g1, e0, e1), "ig_espirit_eig_c64: evals overlaps gram");
-    IG_REQUIRE(ctx, !esp_overlap(m0, m1, e0, e1), "ig_espirit_eig_c64: evals overlaps maps");
+    IG_REQUIRE(ctx, !ig_bytes_overlap(g0, g1, m0, m1), "ig_espirit_eig_c64: maps overlaps gram");
+    IG_REQUIRE(ctx, !ig_bytes_overlap(g0, g1, e0, e1), "ig_espirit_eig_c64: evals overlaps gram");
+    IG_REQUIRE(ctx, !ig_bytes_overlap(m0, m1, e0, e1), "ig_espirit_eig_c64: evals overlaps maps");
     if (int rc = ig_set_device(ctx)) return rc;
     ig_prof_scope prof(ctx, nc <= 8 ? "espirit_eig_jacobi" : "espirit_eig_orth", (double)n * (8.0 * (double)(ntri + nc * nm) + 4.0 * (double)nm));
     const float2* G = (const float2*)gram;
     float2* M = (float2*)maps;
     const int c = (int)nc, m = (int)nm, it = (int)iters;
     if (nc <= 8) {
-        const dim3 grid = esp_grid(n, ESP_JBLK), block(ESP_JBLK);
+        const dim3 grid = ig_grid_1d(n, ESP_JBLK, ESP_MAXGRID), block(ESP_JBLK);
 #define IG_ESP_JAC(NC) hipLaunchKernelGGL((k_esp_jacobi<NC>), grid, block, 0, ctx->stream, n, m, it, crop, G, ldg, M, ldm, evals, lde)
         switch (c) {
             case 1: IG_ESP_JAC(1); break;

@@ -29,22 +29,6 @@ constexpr int MAPS_MAXM = 4;
 constexpr int MAPS_BLK = 256;
 constexpr int64_t MAPS_MAXGRID = 1 << 20;   // workgroups; the item loop strides beyond that
 
-// V neighbouring elements: one 8-byte or one 16-byte access
-template <int V>
-__device__ __forceinline__ void ldm(float2 (&v)[V], const float2* p) {
-    if constexpr (V == 2) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = make_float2(q.x, q.y); v[1] = make_float2(q.z, q.w);
-    } else {
-        v[0] = *p;
-    }
-}
-template <int V>
-__device__ __forceinline__ void stm(float2* p, const float2 (&v)[V]) {
-    if constexpr (V == 2) *reinterpret_cast<float4*>(p) = make_float4(v[0].x, v[0].y, v[1].x, v[1].y);
-    else *p = v[0];
-}
-
 // ---- coil-major -------------------------------------------------------------------------------------------------------------
 // nv work items of V voxels each (n = nv * V); plane = n * nc elements of S per set of maps
 template <int NM, int V, bool BETA>
@@ -57,7 +41,7 @@ k_maps_fwd(int64_t nv, int64_t n, int64_t nc, const float2* __restrict__ S, cons
         float2 xr[NM][V];
 #pragma unroll
         for (int m = 0; m < NM; ++m) {
-            ldm<V>(xr[m], x + i + (int64_t)m * ldi);
+            ldv<V>(xr[m], x + i + (int64_t)m * ldi);
 #pragma unroll
             for (int v = 0; v < V; ++v) xr[m][v] = cmul(a, xr[m][v]);
         }
@@ -71,25 +55,19 @@ k_maps_fwd(int64_t nv, int64_t n, int64_t nc, const float2* __restrict__ S, cons
 #pragma unroll
             for (int m = 0; m < NM; ++m) {
                 float2 s[V];
-                ldm<V>(s, sp + (int64_t)m * plane);
+                ldv<V>(s, sp + (int64_t)m * plane);
 #pragma unroll
                 for (int v = 0; v < V; ++v) cfma(acc[v], s[v], xr[m][v]);
             }
             if (BETA) {
                 float2 o[V];
-                ldm<V>(o, yp);
+                ldv<V>(o, yp);
 #pragma unroll
                 for (int v = 0; v < V; ++v) cfma(acc[v], b, o[v]);
             }
-            stm<V>(yp, acc);
+            stv<V>(yp, acc);
         }
     }
-}
-
-// acc += conj(p) * q
-__device__ __forceinline__ void cfmac(float2& acc, float2 p, float2 q) {
-    acc.x = fmaf(p.x, q.x, acc.x); acc.x = fmaf(p.y, q.y, acc.x);
-    acc.y = fmaf(p.x, q.y, acc.y); acc.y = fmaf(-p.y, q.x, acc.y);
 }
 
 template <int NM, int V, bool BETA>
@@ -109,11 +87,11 @@ k_maps_adj(int64_t nv, int64_t n, int64_t nc, const float2* __restrict__ S, cons
 #pragma unroll 2
         for (int64_t c = 0; c < nc; ++c, sp += n, xp += sc) {
             float2 xv[V];
-            ldm<V>(xv, xp);
+            ldv<V>(xv, xp);
 #pragma unroll
             for (int m = 0; m < NM; ++m) {
                 float2 s[V];
-                ldm<V>(s, sp + (int64_t)m * plane);
+                ldv<V>(s, sp + (int64_t)m * plane);
 #pragma unroll
                 for (int v = 0; v < V; ++v) cfmac(acc[m][v], s[v], xv[v]);
             }
@@ -126,11 +104,11 @@ k_maps_adj(int64_t nv, int64_t n, int64_t nc, const float2* __restrict__ S, cons
             for (int v = 0; v < V; ++v) r[v] = cmul(a, acc[m][v]);
             if (BETA) {
                 float2 o[V];
-                ldm<V>(o, yp);
+                ldv<V>(o, yp);
 #pragma unroll
                 for (int v = 0; v < V; ++v) cfma(r[v], b, o[v]);
             }
-            stm<V>(yp, r);
+            stv<V>(yp, r);
         }
     }
 }
@@ -154,13 +132,13 @@ k_maps_il_fwd(int64_t nitems, int64_t n, int nc, int width, int lg /* log2 G */,
             for (int m = 0; m < NM; ++m) {
                 const float2 xm = cmul(a, x[i + (int64_t)m * ldi]);
                 float2 s[CV];
-                ldm<CV>(s, S + e + (int64_t)m * plane);
+                ldv<CV>(s, S + e + (int64_t)m * plane);
 #pragma unroll
                 for (int v = 0; v < CV; ++v) cfma(acc[v], s[v], xm);
             }
             if (BETA) {
                 float2 o[CV];
-                ldm<CV>(o, y + e);
+                ldv<CV>(o, y + e);
 #pragma unroll
                 for (int v = 0; v < CV; ++v) cfma(acc[v], b, o[v]);
             }
@@ -168,7 +146,7 @@ k_maps_il_fwd(int64_t nitems, int64_t n, int nc, int width, int lg /* log2 G */,
 #pragma unroll
         for (int v = 0; v < CV; ++v)
             if (c0 + v >= nc) acc[v] = make_float2(0.f, 0.f);               // the padding coils: exact zeros
-        stm<CV>(y + e, acc);
+        stv<CV>(y + e, acc);
     }
 }
 
@@ -192,11 +170,11 @@ k_maps_il_adj(int64_t nitems, int64_t n, int nc, int width, int lg, const float2
         if (active && c0 < nc) {
             if (CV == 2 && c0 + 1 < nc) {
                 float2 xv[2];
-                ldm<2>(xv, x + e);
+                ldv<2>(xv, x + e);
 #pragma unroll
                 for (int m = 0; m < NM; ++m) {
                     float2 s[2];
-                    ldm<2>(s, S + e + (int64_t)m * plane);
+                    ldv<2>(s, S + e + (int64_t)m * plane);
                     const float2 p0 = cmulc(s[0], xv[0]), p1 = cmulc(s[1], xv[1]);
                     acc[m] = cadd(p0, p1);
                 }
@@ -228,16 +206,11 @@ k_maps_il_adj(int64_t nitems, int64_t n, int nc, int width, int lg, const float2
     }
 }
 
-dim3 maps_grid(int64_t items) {
-    const int64_t blocks = (items + MAPS_BLK - 1) / MAPS_BLK;
-    return dim3((unsigned)(blocks < MAPS_MAXGRID ? blocks : MAPS_MAXGRID));
-}
-
 template <int NM, int V>
 void maps_launch_cm(ig_ctx* ctx, bool adjoint, bool beta, int64_t n, int64_t nc, const float2* S, const float2* x, float2 a, float2 b,
                     float2* y, int64_t ldi, int64_t sc) {
     const int64_t nv = n / V;
-    const dim3 grid = maps_grid(nv), block(MAPS_BLK);
+    const dim3 grid = ig_grid_1d(nv, MAPS_BLK, MAPS_MAXGRID), block(MAPS_BLK);
     if (adjoint) {
         if (beta) hipLaunchKernelGGL((k_maps_adj<NM, V, true>), grid, block, 0, ctx->stream, nv, n, nc, S, x, sc, a, b, y, ldi);
         else      hipLaunchKernelGGL((k_maps_adj<NM, V, false>), grid, block, 0, ctx->stream, nv, n, nc, S, x, sc, a, b, y, ldi);
@@ -253,7 +226,7 @@ void maps_launch_il(ig_ctx* ctx, bool adjoint, bool beta, int64_t n, int nc, int
     int lg = 0;
     while ((CV << lg) < width) ++lg;
     const int64_t nitems = n << lg;
-    const dim3 grid = maps_grid(nitems), block(MAPS_BLK);
+    const dim3 grid = ig_grid_1d(nitems, MAPS_BLK, MAPS_MAXGRID), block(MAPS_BLK);
     if (adjoint) {
         if (beta) hipLaunchKernelGGL((k_maps_il_adj<NM, CV, true>), grid, block, 0, ctx->stream, nitems, n, nc, width, lg, S, x, a, b, y, ldi);
         else      hipLaunchKernelGGL((k_maps_il_adj<NM, CV, false>), grid, block, 0, ctx->stream, nitems, n, nc, width, lg, S, x, a, b, y, ldi);
@@ -262,8 +235,6 @@ void maps_launch_il(ig_ctx* ctx, bool adjoint, bool beta, int64_t n, int nc, int
         else      hipLaunchKernelGGL((k_maps_il_fwd<NM, CV, false>), grid, block, 0, ctx->stream, nitems, n, nc, width, lg, S, x, ldi, a, b, y);
     }
 }
-
-bool maps_overlap(uintptr_t p0, uintptr_t p1, uintptr_t q0, uintptr_t q1) { return p0 < q1 && q0 < p1; }
 
 }  // namespace
 
@@ -294,8 +265,8 @@ int ig_coil_maps_c64(ig_ctx* ctx, int64_t n, int64_t nc, int64_t nm, const void*
     const uintptr_t x0 = (uintptr_t)x, x1 = x0 + (uintptr_t)(adjoint ? ext_c : ext_i) * sizeof(float2);
     const uintptr_t y0 = (uintptr_t)y, y1 = y0 + (uintptr_t)(adjoint ? ext_i : ext_c) * sizeof(float2);
     const uintptr_t s0 = (uintptr_t)maps, s1 = s0 + (uintptr_t)ext_s * sizeof(float2);
-    IG_REQUIRE(ctx, !maps_overlap(x0, x1, y0, y1), "ig_coil_maps_c64: y overlaps x");
-    IG_REQUIRE(ctx, !maps_overlap(s0, s1, y0, y1), "ig_coil_maps_c64: y overlaps the maps");
+    IG_REQUIRE(ctx, !ig_bytes_overlap(x0, x1, y0, y1), "ig_coil_maps_c64: y overlaps x");
+    IG_REQUIRE(ctx, !ig_bytes_overlap(s0, s1, y0, y1), "ig_coil_maps_c64: y overlaps the maps");
     if (int rc = ig_set_device(ctx)) return rc;
     const bool beta = !(br == 0.f && bi == 0.f);
     const float2 a = make_float2(ar, ai), b = make_float2(br, bi);

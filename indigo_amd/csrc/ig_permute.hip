@@ -97,8 +97,6 @@ k_permute_tile(int64_t n0, int64_t nA, int64_t nB, int64_t sA, int64_t sB, int64
     }
 }
 
-inline int64_t cap(int64_t v, int64_t hi) { return v < 1 ? 1 : (v > hi ? hi : v); }
-
 }  // namespace
 
 int ig_permute3_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, const int perm[3], int64_t ncols,
@@ -127,15 +125,15 @@ int ig_permute3_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, const int p
     const int mode = b0 ? ((ar == 1.f && ai == 0.f) ? 0 : 1) : 2;
     const float2 a = make_float2(ar, ai), b = make_float2(br, bi);
     ig_prof_scope prof(ctx, "permute3", (double)vol * ncols * 8.0 * (b0 ? 2 : 3));
-    const int64_t gz = cap(ncols, MAXY);
+    const int64_t gz = ig_clamp1(ncols, MAXY);
 
     if (p0 == 0) {
         const int64_t nrows = n1 * n2;
         const bool vec = n0 % 2 == 0 && ldx % 2 == 0 && ldy % 2 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0;
         const int64_t per_row = vec ? n0 / 2 : n0;
         // enough blocks for ~8 per CU over all columns; long rows split over grid.x
-        const int64_t gx = cap((per_row + 63) / 64, 64);
-        const int64_t gy = cap((nrows + 3) / 4, MAXY);
+        const int64_t gx = ig_clamp1((per_row + 63) / 64, 64);
+        const int64_t gy = ig_clamp1((nrows + 3) / 4, MAXY);
         const dim3 g((unsigned)gx, (unsigned)gy, (unsigned)gz);
 #define IG_PERM_ROWS(M_, V_) hipLaunchKernelGGL((k_permute_rows<M_, V_>), g, dim3(BLK), 0, ctx->stream, n0, nrows, m1, sin[p1], sin[p2], ncols, \
                                                 (const float2*)x, ldx, a, b, (float2*)y, ldy)
@@ -150,7 +148,7 @@ int ig_permute3_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, const int p
     const int64_t tiles0 = (n0 + PT - 1) / PT, tilesA = (n[A] + PT - 1) / PT;
     IG_REQUIRE(ctx, tiles0 * tilesA <= INT32_MAX, "ig_permute3_c64: %lld x %lld tiles do not fit one grid axis",
                (long long)tiles0, (long long)tilesA);
-    const dim3 g((unsigned)(tiles0 * tilesA), (unsigned)cap(n[B], MAXY), (unsigned)gz);
+    const dim3 g((unsigned)(tiles0 * tilesA), (unsigned)ig_clamp1(n[B], MAXY), (unsigned)gz);
 #define IG_PERM_TILE(M_) hipLaunchKernelGGL((k_permute_tile<M_>), g, dim3(BLK), 0, ctx->stream, n0, n[A], n[B], sin[A], sin[B], sout[0], sout[B], \
                                             tiles0, ncols, (const float2*)x, ldx, a, b, (float2*)y, ldy)
     if (mode == 0) IG_PERM_TILE(0); else if (mode == 1) IG_PERM_TILE(1); else IG_PERM_TILE(2);

@@ -20,22 +20,6 @@ constexpr int TOEP_MAXK = 8;
 constexpr int TOEP_BLK = 256;
 constexpr int64_t TOEP_MAXGRID = 0x7fffffff;   // workgroups of one launch
 
-// V neighbouring elements: one 8-byte or one 16-byte access
-template <int V>
-__device__ __forceinline__ void ldv(float2 (&v)[V], const float2* p) {
-    if constexpr (V == 2) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        v[0] = make_float2(q.x, q.y); v[1] = make_float2(q.z, q.w);
-    } else {
-        v[0] = *p;
-    }
-}
-template <int V>
-__device__ __forceinline__ void stv(float2* p, const float2 (&v)[V]) {
-    if constexpr (V == 2) *reinterpret_cast<float4*>(p) = make_float4(v[0].x, v[0].y, v[1].x, v[1].y);
-    else *p = v[0];
-}
-
 // GV grid points per thread (neighbours in memory: sg == 1), CV coils per access (neighbours in memory: sc == 1); one of the two
 // is 1.  Coil-major: one work item per GV grid points (cpg = 1), which loops over the nloop = nc coils.  Coil-interleaved: a
 // grid point's coils lie side by side, so its cpg = nc / CV groups of coils are cpg neighbouring work items that read the same
@@ -149,8 +133,6 @@ void toep_launch(ig_ctx* ctx, int64_t n, int64_t nc, int nk, const float* kern, 
     hipLaunchKernelGGL((k_psf_mix<NK, GV, CV>), dim3((unsigned)blocks), dim3(TOEP_BLK), 0, ctx->stream, nitems, n, cpg, nloop, nk, kern, x, ldx, y, ldy, sg, sc);
 }
 
-bool toep_overlap(uintptr_t p0, uintptr_t p1, uintptr_t q0, uintptr_t q1) { return p0 < q1 && q0 < p1; }
-
 }  // namespace
 
 int ig_psf_mix_c64(ig_ctx* ctx, int64_t n, int64_t nc, int64_t nk, const float* kern, const void* x, int64_t ldx,
@@ -173,8 +155,8 @@ int ig_psf_mix_c64(ig_ctx* ctx, int64_t n, int64_t nc, int64_t nk, const float* 
     const uintptr_t x0 = (uintptr_t)x, x1 = x0 + (uintptr_t)((nk - 1) * ldx + ext) * sizeof(float2);
     const uintptr_t y0 = (uintptr_t)y, y1 = y0 + (uintptr_t)((nk - 1) * ldy + ext) * sizeof(float2);
     const uintptr_t k0 = (uintptr_t)kern, k1 = k0 + (uintptr_t)(nk * nk * n) * sizeof(float);
-    IG_REQUIRE(ctx, (x == y && ldx == ldy) || !toep_overlap(x0, x1, y0, y1), "ig_psf_mix_c64: y overlaps x (y == x with ldy == ldx is the in-place form)");
-    IG_REQUIRE(ctx, !toep_overlap(k0, k1, y0, y1), "ig_psf_mix_c64: y overlaps the kernel array");
+    IG_REQUIRE(ctx, (x == y && ldx == ldy) || !ig_bytes_overlap(x0, x1, y0, y1), "ig_psf_mix_c64: y overlaps x (y == x with ldy == ldx is the in-place form)");
+    IG_REQUIRE(ctx, !ig_bytes_overlap(k0, k1, y0, y1), "ig_psf_mix_c64: y overlaps the kernel array");
     if ((n * nc + TOEP_BLK - 1) / TOEP_BLK > TOEP_MAXGRID)
         return ig_fail(ctx, IG_ERR_UNSUPPORTED, "ig_psf_mix_c64: %lld x %lld elements per column exceed one launch", (long long)n, (long long)nc);
     if (int rc = ig_set_device(ctx)) return rc;

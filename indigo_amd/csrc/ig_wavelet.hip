@@ -141,8 +141,6 @@ k_csoft(int64_t n0, int64_t n1, int64_t n, int64_t c0, int64_t c1, int64_t c2, i
         }
 }
 
-inline int64_t capg(int64_t v, int64_t hi) { return v < 1 ? 1 : (v > hi ? hi : v); }
-
 int filter_taps(int wavelet) { return wavelet == 0 ? 2 : wavelet == 1 ? 4 : wavelet == 2 ? 8 : 0; }
 
 struct split { int64_t c[3]; int axis; };                         // the box (before the split) and the axis split
@@ -174,9 +172,9 @@ int launch_split(ig_ctx* ctx, const split& sp, const int64_t n[3], int64_t ncols
     // lines (p, q): axis 0 -> (i1, i2); axis 1 -> (i0, i2); axis 2 -> (i0, i1)
     const int pa = a == 0 ? 1 : 0, qa = a == 2 ? 1 : 2;
     const int64_t P = sp.c[pa], Q = sp.c[qa];
-    const int W = a == 0 ? (int)capg(DWT_AX0_ELEMS / d, DWT_STRIP) : DWT_STRIP;
+    const int W = a == 0 ? (int)ig_clamp1(DWT_AX0_ELEMS / d, DWT_STRIP) : DWT_STRIP;
     const size_t lds = (size_t)W * d * sizeof(float2);
-    const dim3 g((unsigned)((P + W - 1) / W), (unsigned)capg(Q, MAXG), (unsigned)capg(ncols, MAXG));
+    const dim3 g((unsigned)((P + W - 1) / W), (unsigned)ig_clamp1(Q, MAXG), (unsigned)ig_clamp1(ncols, MAXG));
     ig_prof_scope prof(ctx, "dwt_lines", (double)sp.c[0] * sp.c[1] * sp.c[2] * ncols * 16.0);
     if (a == 0) {
         auto k = &k_dwt_lines<TAPS, INV, true>;
@@ -195,7 +193,7 @@ int launch_split(ig_ctx* ctx, const split& sp, const int64_t n[3], int64_t ncols
 
 int combine(ig_ctx* ctx, int64_t n, int64_t ncols, const float2* x, int64_t ldx, float2 a, float2 b, float2* y, int64_t ldy,
             bool read_y) {
-    const dim3 g((unsigned)capg((n + 255) / 256, 4096), (unsigned)capg(ncols, MAXG));
+    const dim3 g((unsigned)ig_clamp1((n + 255) / 256, 4096), (unsigned)ig_clamp1(ncols, MAXG));
     ig_prof_scope prof(ctx, "dwt_combine", (double)n * ncols * 8.0 * (read_y ? 3 : 2));
     if (read_y) hipLaunchKernelGGL(k_dwt_combine<true>, g, dim3(256), 0, ctx->stream, n, ncols, x, ldx, a, b, y, ldy);
     else        hipLaunchKernelGGL(k_dwt_combine<false>, g, dim3(256), 0, ctx->stream, n, ncols, x, ldx, a, b, y, ldy);
@@ -275,7 +273,7 @@ int ig_csoft_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t c0, in
     if (vol == 0 || ncols == 0) return IG_OK;
     IG_REQUIRE(ctx, x != nullptr, "ig_csoft_c64: x is NULL");
     if (int rc = ig_set_device(ctx)) return rc;
-    const dim3 g((unsigned)capg((vol + 255) / 256, 4096), (unsigned)capg(ncols, MAXG));
+    const dim3 g((unsigned)ig_clamp1((vol + 255) / 256, 4096), (unsigned)ig_clamp1(ncols, MAXG));
     ig_prof_scope prof(ctx, "csoft", (double)vol * ncols * 16.0);
     hipLaunchKernelGGL(k_csoft, g, dim3(256), 0, ctx->stream, n0, n1, vol, c0, c1, c2, ncols, tau, (float2*)x, ldx);
     IG_LAUNCH_CHECK(ctx, "k_csoft");

@@ -423,8 +423,10 @@ def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', le
     Returns the image as a host (N, 1) array and the objectives logged: [(iteration, value)], every 10 iterations and the last."""
     c64 = np.dtype('complex64')
     T = int(frames)
-    comps = 3 if T == 1 else 4
-    G = B.Gradient(dims) if T == 1 else B.GradientT(dims, T)
+    if T == 1:
+        comps, G, step_fn, step_args = 3, B.Gradient(dims), B.tv_dual_step, (mu, dims)
+    else:
+        comps, G, step_fn, step_args = 4, B.GradientT(dims, T), B.tv4_dual_step, (mu, mu_t, dims, T)
     if step is None:
         L = power_iteration(B, AHA, power_iters)
         log.info("tv: largest eigenvalue of A^H A + lamda I %.6e (%d power iterations)", L, power_iters)
@@ -453,10 +455,7 @@ def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', le
         G.eval(g, v, alpha=1, beta=1, forward=False)
 
     def dual_step(v, xn, xo):
-        if T == 1:
-            B.tv_dual_step(v, xn, xo, sigma, mu, dims)
-        else:
-            B.tv4_dual_step(v, xn, xo, sigma, mu, mu_t, dims, T)
+        step_fn(v, xn, xo, sigma, *step_args)
 
     objectives = []
     work = {}
