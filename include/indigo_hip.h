@@ -258,6 +258,30 @@ int  ig_llr_nuc_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t nt,
 int  ig_basis_c64(ig_ctx* ctx, int64_t n, int64_t nk, int64_t nt, const void* phi, int64_t ldphi, int adjoint,
                   const void* x, int64_t ldx, float alpha_re, float alpha_im, float beta_re, float beta_im,
                   void* y, int64_t ldy);
+/* The two streaming passes of the time-segmented off-resonance model exp(-2 pi i f t) ~ sum_l b_l(t) exp(-2 pi i f tau_l),
+ * tau_l = tau0 + l dtau in seconds (operators.SegmentPhase, Backend.segment_phase, pics --fmap).  No reference
+ * counterpart.  f is a device array of n float32 values of the field map in Hz; x and y are column-major panels, ldx, ldy >= n
+ * in elements, and rows between the columns are never touched.
+ *   adjoint == 0:  y[i, l] = beta*y[i, l] + alpha * exp(-2 pi i f[i] tau_l) * x[i]              (x: n x 1, y: n x L)
+ *   adjoint != 0:  y[i]    = beta*y[i]    + alpha * sum_l exp(+2 pi i f[i] tau_l) * x[i, l]     (x: n x L, y: n x 1)
+ * The product f tau_l is formed in double and reduced to [-1/2, 1/2] cycles before the sine and cosine: every segment's phase
+ * is good to 2e-7 rad whatever the number of cycles.  beta == 0: y is not read.  A y that overlaps x or f is IG_ERR_ARG, with
+ * nothing written.  1 <= L <= 16 and n >= 1, else IG_ERR_UNSUPPORTED.  One pass: 8 n (L + 1) + 4 n bytes, and 8 n (columns of
+ * y) more when beta != 0.                                                                                                      */
+int  ig_fmap_phase_c64(ig_ctx* ctx, int64_t n, int64_t L, const float* f, double tau0, double dtau, int adjoint,
+                       const void* x, int64_t ldx, float alpha_re, float alpha_im, float beta_re, float beta_im,
+                       void* y, int64_t ldy);
+/* Its counterpart on the sample side (operators.SegmentCombine, Backend.segment_combine).  No reference
+ * counterpart.  b is the P x L complex64 interpolator table, a device array, column-major with ldb >= P; row r of the panels
+ * uses row r mod P of the table, and n is a multiple of P (the readout length, or the samples of one coil).
+ *   adjoint == 0:  y[r]    = beta*y[r]    + alpha * sum_l      b[r mod P, l]  * x[r, l]         (x: n x L, y: n x 1)
+ *   adjoint != 0:  y[r, l] = beta*y[r, l] + alpha *       conj(b[r mod P, l]) * x[r]            (x: n x 1, y: n x L)
+ * beta == 0: y is not read.  A y that overlaps x or b, or an n that is no multiple of P, is IG_ERR_ARG, with nothing written.
+ * 1 <= L <= 16 and n >= 1, else IG_ERR_UNSUPPORTED.  One pass: 8 n (L + 1) + 8 P L bytes, and 8 n (columns of y) more when
+ * beta != 0.                                                                                                                   */
+int  ig_fmap_combine_c64(ig_ctx* ctx, int64_t n, int64_t L, int64_t P, const void* b, int64_t ldb, int adjoint,
+                         const void* x, int64_t ldx, float alpha_re, float alpha_im, float beta_re, float beta_im,
+                         void* y, int64_t ldy);
 /* The K x K point-spread mixing pass of the Toeplitz normal operator (operators.ToeplitzNormal, Backend.psf_mix,
  * pics --toeplitz).  No reference counterpart.
  *   y[g, c, k] = sum_k' P[g][k, k'] * x[g, c, k']        g < n grid points, c < nc coils, k < nk

@@ -88,6 +88,10 @@ PROTOTYPES = {
                                    c_void_p, c_int64, c_void_p]),
     "ig_basis_c64":       (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64,
                                    c_float, c_float, c_float, c_float, c_void_p, c_int64]),
+    "ig_fmap_phase_c64":  (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_double, c_double, c_int, c_void_p, c_int64,
+                                   c_float, c_float, c_float, c_float, c_void_p, c_int64]),
+    "ig_fmap_combine_c64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64,
+                                    c_float, c_float, c_float, c_float, c_void_p, c_int64]),
     "ig_psf_mix_c64":     (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64]),
     "ig_coil_maps_c64":   (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p,
                                    c_float, c_float, c_float, c_float, c_void_p, c_int64, c_int64, c_int64]),

@@ -495,6 +495,18 @@ class Backend(object):
         coefficient-major in, T frames stacked frame-major out (see operators.FrameBasis); .H is its adjoint"""
         return op.FrameBasis(self, phi, n, **kwargs)
 
+    def SegmentPhase(self, f, taus, n, **kwargs):
+        """the voxel side of the time-segmented off-resonance model for the field map `f` (n values in Hz) and the L equispaced
+        segment times `taus`, shape (nL, n): one image in, its L segments stacked segment-major out (see operators.SegmentPhase);
+        .H is its adjoint"""
+        return op.SegmentPhase(self, f, taus, n, **kwargs)
+
+    def SegmentCombine(self, b, period, n, **kwargs):
+        """the sample side of the time-segmented off-resonance model for the P x L interpolator table `b` (P = `period`) and `n`
+        sample rows, shape (n, nL): the L segments' samples stacked segment-major in, the samples out (see
+        operators.SegmentCombine); .H is its adjoint"""
+        return op.SegmentCombine(self, b, period, n, **kwargs)
+
     def CoilMaps(self, maps, **kwargs):
         """the soft-SENSE map stack for the host array `maps` = dims + (C, M), shape (N C, N M): M images stacked map-major in, C
         coil images stacked coil-major out (see operators.CoilMaps); .H is its adjoint"""
@@ -789,6 +801,51 @@ class Backend(object):
         assert n >= 1 and x.size == n * cols_x and y.size == n * cols_y, (x.shape, y.shape, p.shape, n)
         v = x.to_host().reshape((n, cols_x), order='F').astype(np.complex128)
         out = (v @ p.conj() if adjoint else v @ p.T) * complex(alpha)
+        if beta != 0:
+            out = out + complex(beta) * y.to_host().reshape((n, cols_y), order='F')
+        y.copy_from(np.asfortranarray(out.astype(_C64).reshape(y.shape, order='F')))
+
+    def segment_phase(self, y, x, f, tau0, dtau, L, n, adjoint=False, alpha=1, beta=0):
+        """y = beta*y + alpha * Phase x (adjoint: Phase^H x), the voxel side of the time-segmented off-resonance model (DESIGN.md
+        §3.15): f is a backend array of `n` float32 values of the field map in Hz, tau_l = tau0 + l dtau in seconds, l < L <= 16.
+        Forward, x is the image of n voxels and y the n x L panel of its segments, or the same as an (n L, 1) vector, segment l in
+        rows [ln, (l+1)n):  y[i, l] = exp(-2 pi i f[i] tau_l) x[i].  Adjoint, x holds the segments and y the image:
+        y[i] = sum_l exp(+2 pi i f[i] tau_l) x[i, l].  The field map is what its float32 values say; the phase is formed in
+        float64.  beta == 0: y is not read; y must not overlap x or f.  Host form in float64 through to_host / copy_from; device
+        backends override it."""
+        n, L = int(n), int(L)
+        if not 1 <= L <= 16:
+            raise RuntimeError("segment_phase: %d segments, between 1 and 16 are supported" % L)
+        cols_x, cols_y = (L, 1) if adjoint else (1, L)
+        assert n >= 1 and f.size == n and x.size == n * cols_x and y.size == n * cols_y, (x.shape, y.shape, f.shape, n, L)
+        taus = float(tau0) + np.arange(L, dtype=np.float64) * float(dtau)
+        ph = np.exp(-2j * np.pi * np.outer(f.to_host().reshape(-1).astype(np.float64), taus))
+        v = x.to_host().reshape((n, cols_x), order='F').astype(np.complex128)
+        out = ((ph.conj() * v).sum(axis=1, keepdims=True) if adjoint else ph * v) * complex(alpha)
+        if beta != 0:
+            out = out + complex(beta) * y.to_host().reshape((n, cols_y), order='F')
+        y.copy_from(np.asfortranarray(out.astype(_C64).reshape(y.shape, order='F')))
+
+    def segment_combine(self, y, x, b, period, n, adjoint=False, alpha=1, beta=0):
+        """y = beta*y + alpha * Combine x (adjoint: Combine^H x), the sample side of the time-segmented off-resonance model
+        (DESIGN.md §3.15): b is the P x L interpolator table as a backend array, P = `period`, L <= 16; row r of the `n` rows uses
+        row r mod P of the table and n is a multiple of P.  Forward, x is the n x L panel of the segments' samples, or the same as
+        an (n L, 1) vector, and y the n samples:  y[r] = sum_l b[r mod P, l] x[r, l].  Adjoint, x holds the samples and y the
+        panel:  y[r, l] = conj(b[r mod P, l]) x[r].  beta == 0: y is not read; y must not overlap x or b.  Host form in float64
+        through to_host / copy_from; device backends override it."""
+        n, P = int(n), int(period)
+        t = b.to_host().astype(np.complex128)
+        assert t.ndim == 2 and t.shape[0] == P, (t.shape, P)
+        L = t.shape[1]
+        if not 1 <= L <= 16:
+            raise RuntimeError("segment_combine: %d segments, between 1 and 16 are supported" % L)
+        if P < 1 or n % P:
+            raise RuntimeError("segment_combine: %d rows are no multiple of the table's period %d" % (n, P))
+        cols_x, cols_y = (1, L) if adjoint else (L, 1)
+        assert n >= 1 and x.size == n * cols_x and y.size == n * cols_y, (x.shape, y.shape, t.shape, n)
+        t = np.tile(t, (n // P, 1))
+        v = x.to_host().reshape((n, cols_x), order='F').astype(np.complex128)
+        out = (t.conj() * v if adjoint else (t * v).sum(axis=1, keepdims=True)) * complex(alpha)
         if beta != 0:
             out = out + complex(beta) * y.to_host().reshape((n, cols_y), order='F')
         y.copy_from(np.asfortranarray(out.astype(_C64).reshape(y.shape, order='F')))

@@ -909,6 +909,33 @@ class HipBackend(Backend):
         self._check(self._L.ig_basis_c64(self._ctx, n, K, T, ctypes.c_void_p(phi._arr), phi._leading_dim, int(bool(adjoint)),
                                          xp, ldx, ar, ai, br, bi, yp, ldy), "ig_basis_c64")
 
+    def segment_phase(self, y, x, f, tau0, dtau, L, n, adjoint=False, alpha=1, beta=0):
+        """Backend.segment_phase on the device (ig_fmap_phase_c64): the image and its segments are the columns of panels with their
+        leading dimensions, or stacked in one column"""
+        assert x.dtype == _C64 and y.dtype == _C64 and f.dtype == np.dtype('float32'), "complex64 panels and a float32 field map"
+        n, L = int(n), int(L)
+        assert f.size == n and f.contiguous, (f.shape, n)
+        cols_x, cols_y = (L, 1) if adjoint else (1, L)
+        (xp, ldx), (yp, ldy) = self._frame_panel(x, n, cols_x), self._frame_panel(y, n, cols_y)
+        ar, ai = _cplx(alpha)
+        br, bi = _cplx(beta)
+        self._check(self._L.ig_fmap_phase_c64(self._ctx, n, L, ctypes.c_void_p(f._arr), ctypes.c_double(float(tau0)),
+                                              ctypes.c_double(float(dtau)), int(bool(adjoint)), xp, ldx, ar, ai, br, bi, yp, ldy),
+                    "ig_fmap_phase_c64")
+
+    def segment_combine(self, y, x, b, period, n, adjoint=False, alpha=1, beta=0):
+        """Backend.segment_combine on the device (ig_fmap_combine_c64): the samples and the segments' samples are the columns of
+        panels with their leading dimensions, or stacked in one column"""
+        assert x.dtype == _C64 and y.dtype == _C64 and b.dtype == _C64, "only complex64 is supported"
+        assert b.ndim == 2 and b.shape[0] == int(period), (b.shape, period)
+        n, (P, L) = int(n), b.shape
+        cols_x, cols_y = (1, L) if adjoint else (L, 1)
+        (xp, ldx), (yp, ldy) = self._frame_panel(x, n, cols_x), self._frame_panel(y, n, cols_y)
+        ar, ai = _cplx(alpha)
+        br, bi = _cplx(beta)
+        self._check(self._L.ig_fmap_combine_c64(self._ctx, n, L, P, ctypes.c_void_p(b._arr), b._leading_dim, int(bool(adjoint)),
+                                                xp, ldx, ar, ai, br, bi, yp, ldy), "ig_fmap_combine_c64")
+
     def coil_maps(self, y, x, maps, n, ncoils, nmaps, adjoint=False, alpha=1, beta=0, interleaved=False, width=None):
         """Backend.coil_maps on the device (ig_coil_maps_c64): the images and the coil-major coil images are the columns of panels
         with their leading dimensions, or stacked in one column; interleaved coil images are one contiguous array"""

@@ -774,6 +774,99 @@ class FrameBasis(MatrixFreeOperator):
             self._backend.frame_basis(y[:, j:j + 1], x[:, j:j + 1], self._matrix_d, self._n, adjoint=not forward, alpha=alpha, beta=beta)
 
 
+class SegmentPhase(MatrixFreeOperator):
+    """The voxel side of the time-segmented off-resonance model, shape (nL, n): the image of `n` voxels times exp(-2 pi i f tau_l)
+    for every one of the L <= 16 segment times `taus` (seconds, equispaced), the segments stacked segment-major, segment l in rows
+    [ln, (l+1)n), as `BlockDiag` expects them.  `f` is the field map in Hz, n real values; it is rounded to float32 once and is
+    from then on what those values say.  .H is the adjoint, image = sum_l exp(+2 pi i f tau_l) * segment l.  The field map goes
+    to the device once, on first evaluation.  With `SegmentCombine` the forward model of pics --fmap."""
+
+    def __init__(self, backend, f, taus, n, **kwargs):
+        try:
+            f = np.asarray(f)
+            if np.iscomplexobj(f):
+                raise TypeError
+            f = np.ascontiguousarray(f.reshape(-1, order='F'), dtype=np.float32)
+            taus = np.asarray(taus, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            raise ValueError("SegmentPhase: the field map and the segment times must be real arrays")
+        self._n = int(n)
+        if self._n < 1:
+            raise ValueError("SegmentPhase: n must be positive, got %s" % (n,))
+        if f.size != self._n:
+            raise ValueError("SegmentPhase: a field map of %d values for n = %d voxels" % (f.size, self._n))
+        L = taus.size
+        if not 1 <= L <= 16:
+            raise ValueError("SegmentPhase: %d segments, between 1 and 16 are supported" % L)
+        if not (np.isfinite(f).all() and np.isfinite(taus).all()):
+            raise ValueError("SegmentPhase: the field map and the segment times must be finite")
+        self._tau0, self._dtau = float(taus[0]), float(taus[1] - taus[0]) if L > 1 else 0.0
+        if L > 2 and np.abs(taus - (self._tau0 + np.arange(L) * self._dtau)).max() > 1e-9 * np.abs(taus).max():
+            raise ValueError("SegmentPhase: the segment times must be equispaced, got %s" % (taus,))
+        self._L = L
+        self._matrix = f
+        self._matrix_d = None
+        kwargs.setdefault('name', 'segment phase')
+        super().__init__(backend, shape=(self._n * L, self._n), **kwargs)
+
+    def _eval(self, y, x, alpha=1, beta=0, forward=True, left=True):
+        if self._matrix_d is None:
+            self._matrix_d = self._backend.copy_array(self._matrix, name=self._name)
+        trace = getattr(self._backend, 'trace', None)
+        if trace is not None:
+            # a single pass: the image and every segment move once (8 B per voxel each), the field map 4 B; beta != 0 reads the output
+            trace.add('segment_phase', nbytes=(8 * self._n * (self._L + 1) + 4 * self._n) * x.shape[1] + (0 if beta == 0 else y.nbytes),
+                      nflops=0, shape=x.shape, forward=forward, name=self._name)
+        args = (self._matrix_d, self._tau0, self._dtau, self._L, self._n)
+        if x.shape[1] == 1:
+            return self._backend.segment_phase(y, x, *args, adjoint=not forward, alpha=alpha, beta=beta)
+        for j in range(x.shape[1]):             # the segments become the columns of a panel inside: one product per column
+            self._backend.segment_phase(y[:, j:j + 1], x[:, j:j + 1], *args, adjoint=not forward, alpha=alpha, beta=beta)
+
+
+class SegmentCombine(MatrixFreeOperator):
+    """The sample side of the time-segmented off-resonance model, shape (n, nL): sample r = sum_l b[r mod P, l] * (sample r of
+    segment l) for the P x L complex64 interpolator table `b`, P = `period`, L <= 16, `n` a multiple of P.  The input is the L
+    segments' samples stacked segment-major, segment l in rows [ln, (l+1)n), as `BlockDiag` leaves them.  P is the readout length
+    when the sample times depend on the readout index alone, or the samples of one coil; the coils repeat the table.  .H is the
+    adjoint, segment l = conj(b[r mod P, l]) * sample r.  The table goes to the device once, on first evaluation.  With
+    `SegmentPhase` the forward model of pics --fmap."""
+
+    def __init__(self, backend, b, period, n, **kwargs):
+        try:
+            b = np.require(np.asarray(b), dtype=_C64, requirements='F')
+        except (TypeError, ValueError):
+            raise ValueError("SegmentCombine: the table does not convert to complex64")
+        if b.ndim != 2:
+            raise ValueError("SegmentCombine: the table must be 2-D (period x segments), got shape %s" % (b.shape,))
+        P, L = b.shape
+        if not 1 <= L <= 16:
+            raise ValueError("SegmentCombine: %d segments, between 1 and 16 are supported" % L)
+        if int(period) != P or P < 1:
+            raise ValueError("SegmentCombine: a table of %d rows for the period %s" % (P, period))
+        self._n = int(n)
+        if self._n < 1 or self._n % P:
+            raise ValueError("SegmentCombine: n = %s rows are no positive multiple of the period %d" % (n, P))
+        self._matrix = b
+        self._matrix_d = None
+        kwargs.setdefault('name', 'segment combine')
+        super().__init__(backend, shape=(self._n, self._n * L), **kwargs)
+
+    def _eval(self, y, x, alpha=1, beta=0, forward=True, left=True):
+        if self._matrix_d is None:
+            self._matrix_d = self._backend.copy_array(self._matrix, name=self._name)
+        P, L = self._matrix.shape
+        trace = getattr(self._backend, 'trace', None)
+        if trace is not None:
+            # a single pass: the samples and every segment move once (8 B per row each), the table once; beta != 0 reads the output
+            trace.add('segment_combine', nbytes=(8 * self._n * (L + 1) + 8 * P * L) * x.shape[1] + (0 if beta == 0 else y.nbytes),
+                      nflops=0, shape=x.shape, forward=forward, name=self._name)
+        if x.shape[1] == 1:
+            return self._backend.segment_combine(y, x, self._matrix_d, P, self._n, adjoint=not forward, alpha=alpha, beta=beta)
+        for j in range(x.shape[1]):             # the segments become the columns of a panel inside: one product per column
+            self._backend.segment_combine(y[:, j:j + 1], x[:, j:j + 1], self._matrix_d, P, self._n, adjoint=not forward, alpha=alpha, beta=beta)
+
+
 class ToeplitzNormal(MatrixFreeOperator):
     """A^H A of a non-Cartesian SENSE problem -- in a temporal subspace of K coefficient images, or K = 1 for one frame -- as ONE
     Toeplitz operator, shape (N K, N K):

@@ -12,6 +12,8 @@ total-variation primal-dual; time frames one by one or in a temporal subspace; s
     python -m indigo_amd.pics [--l1 | --tv | --llr ...] [--crop "MAPS:1"] espirit.npz           (maps with a MAPS axis of length M: soft-SENSE)
     python -m indigo_amd.pics --maps scan.maps.npy ... scan.npz                                  (maps from python -m indigo_amd.ecalib scan.npz)
     python -m indigo_amd.pics --cc V ... scan.npz                                                (V virtual coils: python -m indigo_amd.cc in passing)
+    python -m indigo_amd.pics --fmap B0.npy --dwell 4e-6 [--te 1e-3] [--fmap-segments L] ... scan.npz   (off-resonance correction)
+    python -m indigo_amd.pics --fmap B0.npy --times T.npy [--fmap-tol 1e-3] [--toeplitz] ... scan.npz
 
 The counterpart of the reference's driver script (examples/pics.py:20-95 arguments, data layout and tree
 construction, :179-233 recipe, normal equations, CG, output): reads `data` (k-space), `maps` (coil sensitivities)
@@ -114,6 +116,24 @@ reconstruction sees them: `indigo_amd.cc.compress` with the Gram matrix of all s
 `python -m indigo_amd.cc` writes the compressed scan, takes noise samples and a calibration region).  An iteration then costs V / C
 of what it did.  Data and maps with different coil counts are refused.  Without the flag the driver runs the code it ran before.
 
+Off-resonance.  `--fmap FILE.npy` (a real (X, Y, Z) field map in Hz, stored reversed like the maps; a scan that holds an array
+`fmap` uses it without the flag) corrects the phase exp(-2 pi i f(r) t) that the field inhomogeneity f(r) builds up along a long
+spiral, cone or radial-EPI readout and that no regulariser removes (`bart pics` with a field map, MIRT, sigpy; no counterpart in the
+reference's driver).  The sample times come from `--times FILE.npy` (seconds, (readout,) or (readout, views), stored reversed; a scan
+array `times` counts as the flag) or from `--dwell SECONDS [--te SECONDS]`, t = te + dwell * readout index.  The model is time
+segmentation, exp(-2 pi i f t_j) ~ sum_{l<L} b_l(t_j) exp(-2 pi i f tau_l) with L equispaced tau_l and the histogram-weighted
+least-squares interpolator b of `indigo_amd.fmap.segments` (`--fmap-segments L`, or the smallest L <= 16 whose model error is below
+`--fmap-tol`; the histogram is taken where any coil map is non-zero).  With A0 the tree built as above,
+
+    A = SegmentCombine(b) * BlockDiag([A0] * L) * SegmentPhase(f, tau),        A^H A + lamda I = A^H * A + lamda I_N
+
+(operators.SegmentPhase, operators.SegmentCombine, `Backend.segment_phase`, `Backend.segment_combine`): the L
+segments are L frames that share one trajectory, so they share one tree.  The unknown is the one image of N voxels: CG, `--l1`,
+`--tv` and `--llr` run on it unchanged and the result has the shape of the plain run.  With `--toeplitz`,
+A^H A + lamda I = lamda I + SegmentPhase^H * ToeplitzNormal(K = L) * SegmentPhase, whose L x L point-spread functions are the adjoint
+NUFFTs of conj(b_l) b_l' (L <= 8).  A field map with several time frames, with `--basis` or with M > 1 sets of maps is refused, as
+is a complex one (R2* decay).  Without a field map the driver runs the code it ran before.
+
 Containers: HDF5 (`.h5`, the reference's format; needs h5py, which this image does not ship) or NumPy `.npz` with
 the same three arrays in the same orientation; the result goes back into the HDF5 file as dataset `rec`, or next to
 an `.npz` input as `<name>.rec.npy`.
@@ -168,6 +188,12 @@ def parse(argv):
     ap.add_argument('--toeplitz', action='store_true', help='evaluate A^H A as one Toeplitz operator on the grid of twice the image size (with --basis: K x K point-spread functions, the cost no longer grows with the frames)')
     ap.add_argument('--maps', default=None, help='coil maps from this .npy file, (X, Y, Z, C, M) stored reversed (what python -m indigo_amd.ecalib writes), in place of the scan\'s `maps`')
     ap.add_argument('--cc', type=int, default=None, help='compress the coils of data and maps to this many virtual coils first (indigo_amd.cc: all samples, no whitening)')
+    ap.add_argument('--fmap', default=None, help='off-resonance correction: a real (X, Y, Z) field map in Hz from this .npy file, stored reversed like the maps (a scan array `fmap` is used without the flag)')
+    ap.add_argument('--times', default=None, help='sample times of --fmap in seconds, a .npy file with a (readout,) or (readout, views) array stored reversed (a scan array `times` counts as this flag)')
+    ap.add_argument('--dwell', type=float, default=None, help='sample times of --fmap as te + dwell * readout index, in seconds (instead of --times)')
+    ap.add_argument('--te', type=float, default=None, help='time of the first sample of --dwell in seconds (default 0)')
+    ap.add_argument('--fmap-segments', type=int, default=None, help='time segments of --fmap, 1..16 (default: the smallest count that reaches --fmap-tol)')
+    ap.add_argument('--fmap-tol', type=float, default=1e-3, help='model error (weighted RMS over the field-map histogram) that the automatic choice of --fmap-segments must reach')
     ap.add_argument('data', nargs='?', default="scan.h5", help='k-space data: HDF5 (data/maps/traj) or .npz; maps may hold M <= 4 sets on the MAPS axis (soft-SENSE)')
     args = ap.parse_args(argv)
     if args.llr > 0 and args.l1 > 0:
@@ -184,7 +210,35 @@ def parse(argv):
     if args.toeplitz and args.basis_rank is not None and args.basis_rank > 8:
         ap.error("--toeplitz serves at most 8 coefficient images (--basis-rank %d): its kernel array holds 4 K^2 bytes per point "
                  "of the doubled grid, 137 GB at K = 16 on a 512^3 grid" % args.basis_rank)
+    if args.times is not None and args.dwell is not None:
+        ap.error("--times and --dwell cannot be combined: the sample times come from one of them")
+    if args.te is not None and args.dwell is None:
+        ap.error("--te needs --dwell")
+    if args.dwell is not None and not args.dwell > 0:
+        ap.error("--dwell must be positive")
+    if args.fmap is not None and args.basis is not None:
+        ap.error("--fmap cannot be combined with --basis: the time segments take the place of the frames (a follow-up)")
+    if args.fmap_segments is not None and not 1 <= args.fmap_segments <= 16:
+        ap.error("--fmap-segments must lie between 1 and 16")
+    if args.toeplitz and args.fmap_segments is not None and args.fmap_segments > 8:
+        ap.error("--toeplitz serves at most 8 time segments (--fmap-segments %d): its kernel array holds 4 K^2 bytes per point "
+                 "of the doubled grid, 137 GB at K = 16 on a 512^3 grid" % args.fmap_segments)
+    if not args.fmap_tol > 0:
+        ap.error("--fmap-tol must be positive")
     return args
+
+
+def load_extras(path, names=('fmap', 'times')):
+    """the optional arrays of a scan as stored, {name: array} for those of `names` that the file holds"""
+    if path.endswith(".npz"):
+        z = np.load(path)
+        return {k: z[k] for k in names if k in z}
+    try:
+        import h5py
+    except ImportError:
+        return {}
+    with h5py.File(path, 'r') as hdf:
+        return {k: hdf[k][:] for k in names if k in hdf}
 
 
 def load(path, maps_file=None):
@@ -252,11 +306,13 @@ def subspace_basis(basis, frames, rank=None):
     return np.asfortranarray(phi.astype(np.complex64))
 
 
-def toeplitz_normal(B, mps, distinct, which, phi, lamda, width, osf, recipe=None):
+def toeplitz_normal(B, mps, distinct, which, phi, lamda, width, osf, recipe=None, segments=None):
     """A^H A + lamda I of `reconstruct` in Toeplitz form, with the scratch arena reserved for it.  phi (T x K): one
     `ToeplitzNormal` of K coefficient images; phi None: one `ToeplitzNormal` (K = 1) per distinct trajectory, each + lamda I, under a
     `BlockDiag` over the frames `which`, or alone for one frame.  distinct: the trajectories (3, readout, views) in cycles per pixel;
-    recipe: the pass list of the run's own trees, for the set-up transform of `psf_kernel`."""
+    recipe: the pass list of the run's own trees, for the set-up transform of `psf_kernel`.
+    segments = (Phase, weights), the `SegmentPhase` of a field-map run and the (samples, L) expansion of its interpolator: one
+    `ToeplitzNormal` of the L segments between Phase and Phase^H."""
     from indigo_amd.operators import ToeplitzNormal
     from indigo_amd.toeplitz import psf_kernel
     from indigo_amd.transforms import reserve_for
@@ -264,6 +320,14 @@ def toeplitz_normal(B, mps, distinct, which, phi, lamda, width, osf, recipe=None
     N = int(np.prod(dims))
     maps = mps.reshape(dims + (-1,))
     order = ToeplitzNormal.memory_order(B, dims)
+    if segments is not None:
+        Phase, weights = segments
+        L = weights.shape[1]
+        kern = psf_kernel(B, dims, distinct, which, None, width, osf, order=order, recipe=recipe, sample_weights=weights)
+        AHA = lamda * B.Eye(N) + Phase.H * B.ToeplitzNormal(dims, maps, kern, L, order=order, name='toeplitz segments') * Phase
+        AHA._name = 'SENSE off-resonance (Toeplitz)'
+        reserve_for(AHA, 1, slack_products=6)
+        return AHA
     if phi is not None:
         K = phi.shape[1]
         kern = psf_kernel(B, dims, distinct, which, phi, width, osf, order=order, recipe=recipe)
@@ -485,7 +549,8 @@ def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', le
 
 def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, width=3, fuse=True,
                 l1=0.0, wavelet='db2', levels=3, power_iters=15, step=None, tv=0.0, tv_sigma=None, tv_time=0.0,
-                llr=0.0, llr_block=8, llr_shifts=False, llr_seed=0, basis=None, basis_rank=None, toeplitz=False):
+                llr=0.0, llr_block=8, llr_shifts=False, llr_seed=0, basis=None, basis_rank=None, toeplitz=False,
+                fmap=None, times=None, fmap_segments=None, fmap_tol=1e-3):
     """ksp: (1, readout, views, C, 1, ..., T), mps: (X, Y, Z, C, M), traj: (3, readout, views[, 1, ..., T]) in pixels -> image
     (X, Y, Z, 1, M, ..., T).  T > 1 time frames: the block-diagonal problem of the module docstring, one A_t per frame.
     M > 1 sets of maps: soft-SENSE, M images per frame (module docstring); not with tv_time, basis or toeplitz.
@@ -494,7 +559,10 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
     (`llr_term`) in the prox slot of whichever of the two applies, in place of the wavelet term; else CG on the normal equations.
     basis: a T x K array (its first basis_rank columns): the temporal-subspace problem of the module docstring, whose unknowns and
     result are the K coefficient images (X, Y, Z, 1, 1, 1, K); every regulariser then acts on those.
-    toeplitz: A^H A of every solver is `operators.ToeplitzNormal` (module docstring); A^H y still comes from the gridding operator"""
+    toeplitz: A^H A of every solver is `operators.ToeplitzNormal` (module docstring); A^H y still comes from the gridding operator
+    fmap: a real (X, Y, Z) field map in Hz, with times: the sample times in seconds, (readout,) or (readout, views): the
+    time-segmented off-resonance model of the module docstring with fmap_segments segments (None: the fewest that reach the model
+    error fmap_tol); one frame, one set of maps, no basis.  The unknown and the result are those of the plain run."""
     from indigo_amd.transforms import FuseZpadFFT, Optimize, sense_recipe, soft_sense_tree
     from indigo_amd.transforms import reserve_for
     ksp = np.asarray(ksp, dtype=np.complex64)
@@ -545,6 +613,40 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
         if toeplitz and K > 8:
             raise ValueError("--toeplitz: %d coefficients, at most 8 are supported: the kernel array holds 4 K^2 bytes per point of the "
                              "doubled grid, %.1f GB here (--basis-rank keeps the first K columns)" % (K, 32e-9 * K * K * int(np.prod(mps.shape[:3]))))
+    seg = None
+    if fmap is not None:
+        from indigo_amd import fmap as fmap_mod
+        fmap = np.asarray(fmap)
+        if np.iscomplexobj(fmap):
+            raise ValueError("--fmap: the field map is complex: only a real one in Hz is supported (R2* decay in the imaginary part "
+                             "is a follow-up)")
+        if basis is not None:
+            raise ValueError("--fmap cannot be combined with --basis: the time segments take the place of the frames (a follow-up)")
+        if T > 1:
+            raise ValueError("--fmap cannot be combined with %d time frames: the time segments take the place of the frames (a follow-up)" % T)
+        if M > 1:
+            raise ValueError("--fmap cannot be combined with M = %d sets of maps: the segments' BlockDiag takes one image per segment "
+                             "(a follow-up)" % M)
+        if times is None:
+            raise ValueError("--fmap needs the sample times: give --times FILE.npy or --dwell SECONDS [--te SECONDS]")
+        fmap = fmap.reshape(fmap.shape[:3] + (-1,))[..., 0] if fmap.ndim > 3 and int(np.prod(fmap.shape[3:])) == 1 else fmap
+        if fmap.shape != tuple(mps.shape[:3]):
+            raise ValueError("--fmap: the field map has shape %s, the maps have %s" % (fmap.shape, tuple(mps.shape[:3])))
+        times = np.asarray(times, dtype=np.float64)
+        times = times.reshape(times.shape[:2]) if times.ndim > 2 and int(np.prod(times.shape[2:])) == 1 else times
+        if times.ndim == 2 and times.shape[1] == 1 and ksp.shape[2] != 1:
+            times = times[:, 0]
+        if times.shape not in ((ksp.shape[1],), tuple(ksp.shape[1:3])):
+            raise ValueError("--times: the sample times have shape %s, the k-space has %d readout points and %d views: (readout,) or "
+                             "(readout, views) is expected" % (times.shape, ksp.shape[1], ksp.shape[2]))
+        mask = (np.abs(mps.reshape(mps.shape[:3] + (-1,))) > 0).any(axis=3)
+        seg = fmap_mod.segments(fmap.astype(np.float32), times, L=fmap_segments, mask=mask, tol=fmap_tol)
+        if toeplitz and seg[0].size > 8:
+            raise ValueError("--toeplitz: %d time segments, at most 8 are supported: the kernel array holds 4 K^2 bytes per point of the "
+                             "doubled grid, %.1f GB here (--fmap-segments fixes their number)"
+                             % (seg[0].size, 32e-9 * seg[0].size ** 2 * int(np.prod(mps.shape[:3]))))
+    elif times is not None:
+        log.info("sample times without a field map have no effect")
     recipe = sense_recipe(level)
     if fuse and level >= 3:
         recipe = recipe + [FuseZpadFFT]
@@ -571,7 +673,19 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
     if T == 1:
         distinct, which = [traj.reshape(traj.shape[:3])], [0]
         A, AHA = frame_operators(distinct[0])
-        reserve_for(AHA, 1, slack_products=6)
+        if seg is None:
+            reserve_for(AHA, 1, slack_products=6)
+        else:
+            # the L segments are L frames on one trajectory: one tree under the BlockDiag.  Around it the product holds two panels
+            # of the segments' images and two of their samples
+            taus, table, period, _ = seg
+            N, L, rows = int(np.prod(mps.shape[:3])), taus.size, A.shape[0]
+            reserve_for(AHA, 1, slack_products=6, extra=2 * ((N * L + 31) // 32 * 32) + 2 * ((rows * L + 31) // 32 * 32))
+            Phase = B.SegmentPhase(fmap.reshape(-1, order='F'), taus, N, name='segment phase')
+            A = B.SegmentCombine(table, period, rows, name='segment combine') * B.BlockDiag([A] * L, name='SENSE1 segments') * Phase
+            A._name = 'SENSE1 off-resonance'
+            AHA = (A.H * A) + lamda * B.Eye(N)
+            AHA._name = 'SENSE off-resonance'
     else:
         # frames with equal trajectories share one tree: its matrices are built and uploaded once, and BlockDiag evaluates the
         # same child on each of those frames' rows in turn
@@ -615,7 +729,12 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
         if T > 1:
             del trees, worst
         B._scratch = None
-        AHA = toeplitz_normal(B, mps, distinct, which, phi, lamda, width, osf, recipe=recipe)
+        if seg is not None:
+            Phase = B.SegmentPhase(fmap.reshape(-1, order='F'), seg[0], int(np.prod(mps.shape[:3])), name='segment phase')
+            weights = np.tile(seg[1], (int(np.prod(ksp.shape[1:3])) // seg[2], 1))
+            AHA = toeplitz_normal(B, mps, distinct, which, None, lamda, width, osf, recipe=recipe, segments=(Phase, weights))
+        else:
+            AHA = toeplitz_normal(B, mps, distinct, which, phi, lamda, width, osf, recipe=recipe)
         log.info("tree:\n%s", AHA.dump())
     if tv_time > 0 and T == 1:
         log.info("--tv-time %g has no effect on a scan with one time frame", tv_time)
@@ -650,12 +769,22 @@ def main(argv=None, backend=None):
         from indigo_amd.backends import get_backend
         backend = get_backend(args.backend, device_id=args.device)
     log.info("using backend: %s", type(backend).__name__)
+    extras = load_extras(args.data)                      # (before `load`, which keeps an HDF5 file open for the result)
     data, maps, traj, write = load(args.data, args.maps)
     basis = np.load(args.basis) if args.basis is not None else None
     crops = crop_limits(args.crop)
     ksp = data[tuple(slice(0, min(n, c)) for n, c in zip(data.shape, crops[-data.ndim:]))].T
     mps = maps[tuple(slice(0, min(n, c)) for n, c in zip(maps.shape, crops[-maps.ndim:]))].T
     trj = traj[tuple(slice(0, min(n, c)) for n, c in zip(traj.shape, crops[-traj.ndim:]))].T
+    fmap = np.load(args.fmap).T if args.fmap is not None else extras['fmap'].T if 'fmap' in extras else None
+    if args.times is not None or 'times' in extras:
+        if args.dwell is not None:
+            raise ValueError("--dwell cannot be combined with the scan's own `times`: the sample times come from one of them")
+        times = (np.load(args.times) if args.times is not None else extras['times']).T
+    elif args.dwell is not None:
+        times = (args.te or 0.0) + args.dwell * np.arange(ksp.shape[1], dtype=np.float64)
+    else:
+        times = None
     if args.cc is not None:
         from indigo_amd import cc
         ksp, mps = cc.compress(backend, ksp, mps, V=args.cc)[:2]
@@ -663,7 +792,8 @@ def main(argv=None, backend=None):
                       width=args.width, fuse=not args.no_fuse, l1=args.l1, wavelet=args.wavelet, levels=args.levels,
                       power_iters=args.power_iters, step=args.step, tv=args.tv, tv_sigma=args.tv_sigma, tv_time=args.tv_time,
                       llr=args.llr, llr_block=args.llr_block, llr_shifts=args.llr_shifts, llr_seed=args.llr_seed,
-                      basis=basis, basis_rank=args.basis_rank, toeplitz=args.toeplitz)
+                      basis=basis, basis_rank=args.basis_rank, toeplitz=args.toeplitz,
+                      fmap=fmap, times=times, fmap_segments=args.fmap_segments, fmap_tol=args.fmap_tol)
     write(img.T)
     log.info("reconstruction complete")
     return img

@@ -54,7 +54,7 @@ def pack_planes(P, order='xyz'):
     return out
 
 
-def psf_kernel(B, dims, trajs, which, phi, width, osf, order='xyz', recipe=None):
+def psf_kernel(B, dims, trajs, which, phi, width, osf, order='xyz', recipe=None, sample_weights=None):
     """The kernel array of `ToeplitzNormal` for an image of `dims` voxels: host float32 (K^2, 8 prod dims), planes as in
     `pack_planes`, in the grid memory order `order`.
 
@@ -63,6 +63,10 @@ def psf_kernel(B, dims, trajs, which, phi, width, osf, order='xyz', recipe=None)
     phi     the T x K temporal basis, or None: K = 1 with a weight of one per frame (one frame: which = [0])
     width, osf   the Kaiser-Bessel half-width and the oversampling of the run's own NUFFT: q_t is computed with the same
     recipe  optional pass list (indigo_amd.transforms.Optimize) for the set-up transform's tree
+    sample_weights   optional (samples, L) complex array for ONE trajectory and no basis, the per-sample interpolator of a
+            time-segmented field-map model (indigo_amd.fmap): K = L, and pair (a, b) is the adjoint NUFFT of
+            conj(w[:, a]) w[:, b] in place of W[a, b] times that of ones: L (L + 1) / 2 set-up transforms.  The kernel stays
+            Hermitian at every grid point, psf_ba[d] = conj(psf_ab[-d]).  None: the planes are what they were without it.
 
     q_t is computed once per distinct trajectory: B.NUFFT(..., N = 2 dims).H applied to ones.  The sample at image index j is the
     lag d = j - dims (the centred transform's origin), and psf[d] belongs at index d mod 2 dims: a circular shift by half the
@@ -77,6 +81,14 @@ def psf_kernel(B, dims, trajs, which, phi, width, osf, order='xyz', recipe=None)
     P = int(np.prod(grid))
     which = [int(w) for w in which]
     T = len(which)
+    if sample_weights is not None:
+        if phi is not None or T != 1 or len(trajs) != 1:
+            raise ValueError("psf_kernel: sample weights go with one trajectory, one frame and no basis")
+        sample_weights = np.asarray(sample_weights, dtype=np.complex128)
+        nsamp = int(np.prod(np.asarray(trajs[0]).shape[1:]))
+        if sample_weights.ndim != 2 or sample_weights.shape[0] != nsamp:
+            raise ValueError("psf_kernel: sample weights of shape %s for %d samples" % (sample_weights.shape, nsamp))
+        phi = np.ones((1, sample_weights.shape[1]), dtype=np.complex128)        # (its shape only: K = L)
     phi = np.ones((T, 1), dtype=np.complex128) if phi is None else np.asarray(phi, dtype=np.complex128)
     if phi.ndim != 2 or phi.shape[0] != T:
         raise ValueError("psf_kernel: a basis of shape %s for %d frames" % (phi.shape, T))
@@ -96,6 +108,15 @@ def psf_kernel(B, dims, trajs, which, phi, width, osf, order='xyz', recipe=None)
         if recipe:
             F = Optimize(recipe).visit(B.KronI(1, F) * B.VStack([B.Diag(np.ones(grid + (1,), dtype=_C64))], name='maps'))
         reserve_for(F, 1, slack_products=4)
+        if sample_weights is not None:
+            for a, b in pairs:
+                w = (sample_weights[:, a].conj() * sample_weights[:, b]).astype(_C64).reshape((-1, 1))
+                w = B.copy_array(np.asfortranarray(w), name='psf.weights')
+                vols[(a, b)] = B.zero_array((P, 1), _C64, name='psf.%d.%d' % (a, b))
+                F.H.eval(vols[(a, b)], w)
+                del w
+            del F
+            continue
         ones = B.copy_array(np.ones((F.shape[0], 1), dtype=_C64, order='F'), name='psf.ones')
         q = B.zero_array((P, 1), _C64, name='psf.q')
         F.H.eval(q, ones)
