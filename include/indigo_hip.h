@@ -347,6 +347,20 @@ int  ig_espirit_eig_c64(ig_ctx* ctx, int64_t n, int64_t nc, int64_t nm, int64_t 
  * ceil(n / slab) are never touched.  A parts that overlaps x is IG_ERR_ARG, with nothing written.  1 <= nc <= 64, n >= 1 and
  * slab >= 1, else IG_ERR_UNSUPPORTED.  One pass: 8 n nc bytes read, 4 nc^2 n real flops.                                          */
 int  ig_coil_gram_c64(ig_ctx* ctx, int64_t n, int64_t nc, const void* x, int64_t ldx, int64_t slab, void* parts, int64_t ldp);
+/* Dictionary matching: the atom that best explains each voxel's subspace coefficients (indigo_amd.dictmatch, Backend.dict_match;
+ * DESIGN.md §3.16).  No reference counterpart.  x is a device column-major panel of n voxels x nk coefficients (coefficient image k is
+ * column k, ldx >= n in elements); d is the device nk x na dictionary, column-major with ldd >= nk: atom a is column a, and the caller
+ * normalises the atoms.  For voxel i with c = x[i, :]
+ *     s_a = |d_a^H c|^2 = |sum_k conj(d[k, a]) c[k]|^2
+ * idx[i] (n int32) is the smallest a that attains max_a s_a as computed in float32, and ip[i] (n complex64) = d_a^H c for that a.  A
+ * zero voxel gives idx = 0 and ip = 0.  The n x na scores are never stored: a fused product-and-arg-max on float32-input MFMA over
+ * [Re c | Im c] (exact float32 products, one rounding per product; Re and Im of d_a^H c are chains of 2 nk fmas), a running maximum
+ * per voxel.  Deterministic: no atomics and a fixed order, two calls give the same bits.  Rows of x below n and rows of d below nk
+ * (the padding of a leading dimension) are never read, x and d are never written.  An idx or ip that overlaps x or d, or the other
+ * output, is IG_ERR_ARG, with nothing written.  1 <= nk <= 32, 1 <= na < 2^31 and n >= 1, else IG_ERR_UNSUPPORTED.
+ * One pass: 8 nk + 12 bytes per voxel (the dictionary, 8 nk na bytes, stays in the L2), 8 nk na real flops per voxel.            */
+int  ig_dict_match_c64(ig_ctx* ctx, int64_t n, int64_t nk, int64_t na, const void* x, int64_t ldx, const void* d, int64_t ldd,
+                       int32_t* idx, void* ip);
 
 /* ------------------------------------------------------------------------
  * CSR x dense-panel SpMM.  Replaces Backend.ccsrmm

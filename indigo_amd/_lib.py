@@ -99,6 +99,7 @@ PROTOTYPES = {
     "ig_espirit_eig_c64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_float, c_void_p, c_int64, c_void_p, c_int64,
                                    c_void_p, c_int64]),
     "ig_coil_gram_c64":   (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64]),
+    "ig_dict_match_c64":  (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "ig_ccsrmm_il":     (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64,
                                    c_float, c_float, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_float, c_float, c_void_p, c_int64]),

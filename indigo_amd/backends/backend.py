@@ -982,6 +982,29 @@ class Backend(object):
         phi = self.copy_array(np.asfortranarray(A.conj().T.astype(_C64)), name='cc.phi')
         self.frame_basis(y, x, phi, n, adjoint=True)
 
+    def dict_match(self, x, atoms, n, chunk=1 << 16):
+        """The atom of a dictionary that best explains each of `n` voxels' subspace coefficients (indigo_amd.dictmatch, DESIGN.md
+        §3.16).  x is the n x K panel of the coefficient images (with its leading dimension), or the same as an (n K, 1) vector, as
+        `frame_basis` takes it; atoms is the K x N dictionary as a backend array, atom a in column a, normalised by the caller.  With
+        c = x[i, :] and s_a = |d_a^H c|^2, returns the host arrays (idx int32[n], ip complex64[n]): idx[i] the smallest a that attains
+        max_a s_a, ip[i] = d_a^H c for that a; a zero voxel gives (0, 0).  Neither input is written.  K <= 32.  Host form in float64
+        through to_host, `chunk` voxels at a time (a chunk x N matrix of scores); device backends override it."""
+        n = int(n)
+        assert atoms.ndim == 2, atoms.shape
+        K, N = atoms.shape
+        if not 1 <= K <= 32:
+            raise RuntimeError("dict_match: %d coefficients, between 1 and 32 are supported" % K)
+        assert n >= 1 and N >= 1 and x.size == n * K, (x.shape, atoms.shape, n)
+        D = atoms.to_host().astype(np.complex128).conj()
+        v = x.to_host().reshape((n, K), order='F')
+        idx, ip = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=_C64)
+        for i0 in range(0, n, max(1, int(chunk))):
+            P = v[i0:i0 + chunk].astype(np.complex128) @ D
+            best = np.argmax(P.real ** 2 + P.imag ** 2, axis=1)                # (the first of equal maxima: the lowest index)
+            idx[i0:i0 + chunk] = best
+            ip[i0:i0 + chunk] = P[np.arange(P.shape[0]), best]
+        return idx, ip
+
     @staticmethod
     def psf_unpack(kern, n, K):
         """the (n, K, K) complex128 Hermitian matrices of a `psf_mix` kernel array: K^2 planes of n floats, the K real diagonals,

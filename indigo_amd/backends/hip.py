@@ -997,6 +997,19 @@ class HipBackend(Backend):
         total = np.add.reduce(parts, axis=0, dtype=np.complex128)
         return self.espirit_unpack(total.reshape((1, -1)), 1, C)[0]
 
+    def dict_match(self, x, atoms, n, chunk=None):
+        """Backend.dict_match on the device (ig_dict_match_c64): the coefficient images are the columns of a panel with its leading
+        dimension, or stacked in one column; one launch for all n voxels (`chunk` has no meaning here)"""
+        assert x.dtype == _C64 and atoms.dtype == _C64, "only complex64 is supported"
+        assert atoms.ndim == 2, atoms.shape
+        n, (K, N) = int(n), atoms.shape
+        xp, ldx = self._frame_panel(x, n, K)
+        idx = self.empty_array((n, 1), np.dtype('int32'), name='dict.idx')
+        ip = self.empty_array((n, 1), _C64, name='dict.ip')
+        self._check(self._L.ig_dict_match_c64(self._ctx, n, K, N, xp, ldx, ctypes.c_void_p(atoms._arr), atoms._leading_dim,
+                                              ctypes.c_void_p(idx._arr), ctypes.c_void_p(ip._arr)), "ig_dict_match_c64")
+        return idx.to_host().ravel(), ip.to_host().ravel()
+
     def psf_mix(self, y, x, kern, n, ncoils, interleaved=False, width=None):
         """Backend.psf_mix on the device (ig_psf_mix_c64): the K images are the columns of panels with their leading
         dimensions, or stacked in one column; y may be x"""

@@ -19,7 +19,7 @@ OBJDIR = os.path.join(HERE, "lib", "obj")
 LIBNAME = "libindigo_hip.so"
 
 SOURCES = ["ig_fft_abd0.hip", "ig_fft_abd1.hip", "ig_fft_abd2.hip", "ig_fft_abd3.hip", "ig_fft.hip", "ig_spmm.hip", "ig_gridsep.hip", "ig_context.hip", "ig_blas.hip",
-           "ig_permute.hip", "ig_wavelet.hip", "ig_tv.hip", "ig_llr.hip", "ig_basis.hip", "ig_fmap.hip", "ig_toep.hip", "ig_maps.hip", "ig_espirit.hip", "ig_cc.hip", "ig_comm.hip", "ig_interp.hip", "ig_dense.hip"]       # (the slow ones first: four compile side by side)
+           "ig_permute.hip", "ig_wavelet.hip", "ig_tv.hip", "ig_llr.hip", "ig_basis.hip", "ig_fmap.hip", "ig_toep.hip", "ig_maps.hip", "ig_espirit.hip", "ig_cc.hip", "ig_dict.hip", "ig_comm.hip", "ig_interp.hip", "ig_dense.hip"]       # (the slow ones first: four compile side by side)
 ARCH = "gfx950"
 CXXFLAGS = [
     "--offload-arch=%s" % ARCH, "-O3", "-std=c++17", "-fPIC",
@@ -39,6 +39,11 @@ EXTRA_FLAGS = {
     # the SLP vectoriser turns the complex products into v_pk_fma_f32 and keeps a negated and swapped copy of every loop-invariant
     # matrix element for them: k_esp_orth held 3 x its 128 matrix registers and spilled (up to 1.4 KB of scratch per lane)
     "ig_espirit.hip": ["-fno-slp-vectorize"],
+    # the arg-max epilogue of k_dict_match reads every accumulator with the VALU: left to itself the compiler keeps 64-128 of them
+    # in AGPRs and pays one v_accvgpr_read each (128 of the 384 VALU instructions per tile at K = 4); with the results in VGPRs and
+    # without the packed squares' gathering moves the tile takes 256 (measured at 256^3 x 4096 atoms: 25.7 -> 22.7 ms at K = 4,
+    # 40.6 -> 37.9 ms at K = 8).  No scratch either way.
+    "ig_dict.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
     # host-only double-precision arithmetic that must round like the reference's (numpy / numba): no fused multiply-add
     "ig_interp.hip": ["-ffp-contract=off"],
 }
