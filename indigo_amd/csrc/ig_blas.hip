@@ -204,7 +204,7 @@ k_reduce(int64_t n, const float2* __restrict__ x, const float2* __restrict__ y, 
 }
 
 __global__ void __launch_bounds__(BLK)
-k_reduce_final(int nblocks, const double* __restrict__ partials, double* __restrict__ out) {
+k_reduce_final(int nblocks, const double* __restrict__ partials, double* __restrict__ out, int nout) {
     double re = 0, im = 0;
     for (int i = threadIdx.x; i < nblocks; i += BLK) { re += partials[2 * i]; im += partials[2 * i + 1]; }
     re = wave_sum(re); im = wave_sum(im);
@@ -215,7 +215,8 @@ k_reduce_final(int nblocks, const double* __restrict__ partials, double* __restr
     if (threadIdx.x == 0) {
         double r = 0, m = 0;
         for (int w = 0; w < BLK / 64; ++w) { r += s_re[w]; m += s_im[w]; }
-        out[0] = r; out[1] = m;
+        out[0] = r;
+        if (nout > 1) out[1] = m;                                  // (a norm's caller owns one double only)
     }
 }
 
@@ -405,10 +406,12 @@ __global__ void k_scalar_copy(double* __restrict__ dst, const double* __restrict
     for (int i = threadIdx.x; i < count; i += blockDim.x) dst[i] = src[i];
 }
 
-// the same two-kernel deterministic reduction, result left on the device (d_out[0..1]); no host synchronisation
+// the same two-kernel deterministic reduction, result left on the device (dot: d_out[0..1]; norm: d_out[0] and nothing
+// behind it); no host synchronisation
 int reduce_dev(ig_ctx* ctx, bool dot, int64_t n, const void* x, const void* y, double* d_out) {
     if (int rc = ig_set_device(ctx)) return rc;
-    if (n == 0) { IG_HIP(ctx, hipMemsetAsync(d_out, 0, 2 * sizeof(double), ctx->stream)); return IG_OK; }
+    const int nout = dot ? 2 : 1;
+    if (n == 0) { IG_HIP(ctx, hipMemsetAsync(d_out, 0, nout * sizeof(double), ctx->stream)); return IG_OK; }
     int g = grid_for(ctx, n);
     if (g > IG_MAX_RED_BLOCKS) g = IG_MAX_RED_BLOCKS;
     ig_prof_scope prof(ctx, dot ? "cdotc" : "scnrm2", (double)n * 8.0 * (dot ? 2 : 1));
@@ -417,7 +420,7 @@ int reduce_dev(ig_ctx* ctx, bool dot, int64_t n, const void* x, const void* y, d
     else
         hipLaunchKernelGGL(k_reduce<false>, dim3(g), dim3(BLK), 0, ctx->stream, n, (const float2*)x, (const float2*)x, ctx->d_partials);
     IG_LAUNCH_CHECK(ctx, "k_reduce");
-    hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(BLK), 0, ctx->stream, g, ctx->d_partials, d_out);
+    hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(BLK), 0, ctx->stream, g, ctx->d_partials, d_out, nout);
     IG_LAUNCH_CHECK(ctx, "k_reduce_final");
     return IG_OK;
 }
@@ -437,7 +440,7 @@ int reduce_common(ig_ctx* ctx, bool dot, int64_t n, const void* x, const void* y
     IG_LAUNCH_CHECK(ctx, "k_reduce");
     // the final (re, im) pair lives in the extra slot behind the per-block partials
     double* d_out = ctx->d_partials + 2 * IG_MAX_RED_BLOCKS;
-    hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(BLK), 0, ctx->stream, g, ctx->d_partials, d_out);
+    hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(BLK), 0, ctx->stream, g, ctx->d_partials, d_out, 2);
     IG_LAUNCH_CHECK(ctx, "k_reduce_final");
     IG_HIP(ctx, hipMemcpyAsync(ctx->h_result, d_out, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     IG_HIP(ctx, hipStreamSynchronize(ctx->stream));
