@@ -23,33 +23,20 @@
 // Besides this row-slot gather (k_csrmm_gather, and k_csrmm_gather_v with 16-byte loads over row-major panels) the
 // file holds the kernels for matrices with mostly empty rows (transposed gridding matrices): k_csrmm_dense64 (64
 // nonzeros per trip, one per lane, LDS segmented sums), k_csrmm_rowlane (a row per lane), the deferred-row kernels for
-// the few very long rows, the panel repacking kernels, and the scatter form of the adjoint.
+// the few very long rows, the panel repacking kernels, and the scatter form of the adjoint; then the brick-binned adjoint gridding
+// of narrow panels (k_grid_bricks, k_grid_slots, the host builders of the brick formats).  Those two kernels stay in this unit because
+// the gather kernels' code depends on them: they are the only callers that leave __shfl's width to its default, and without such a
+// caller the compiler specialises the HIP header's __shfl for width 64 and 178 gather kernels come out with other instructions.
+// The 64-column brick kernels are ig_spmm_bricks.hip, the run-format forward product ig_spmm_runs.hip; ig_spmm_common.h: what they share.
 //
 // Everything here is bandwidth/latency bound integer+fp32 work: no MFMA.
-#include "ig_common.h"
+#include "ig_spmm_common.h"
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
-#include <vector>
-#include <thread>
-#include <atomic>
-#include <functional>
 #include <algorithm>
+#include <atomic>
 #include <cstring>
-#include <cstdlib>
 
 namespace {
-
-constexpr int BLK = 256;
-constexpr int WAVES_PER_BLOCK = BLK / 64;
-
-// Blocks are dealt round-robin to the 8 XCDs (each with a private L2).  Give
-// each XCD a contiguous range of row blocks so neighbouring rows -- which in
-// gridding matrices touch neighbouring panel rows -- share one L2.  Speed
-// only; the map is a bijection for every grid size.
-__device__ __forceinline__ int64_t xcd_block(int64_t b, int64_t nb) {
-    const int64_t q = nb >> 3, rem = nb & 7;
-    const int64_t xcd = b & 7, idx = b >> 3;
-    return (xcd < rem) ? xcd * (q + 1) + idx : rem * (q + 1) + (xcd - rem) * q + idx;
-}
 
 // ---- deferred rows ---------------------------------------------------------------
 // Gridding transposes have a few rows that are orders of magnitude longer than the
@@ -413,220 +400,6 @@ k_csrmm_gather_tile64(int64_t M, int64_t nnz, const int32_t* __restrict__ rowptr
     for (int col = wv; col < 64; col += NW) {
         float2 out = cmul(alpha, tile[tr * TLD + col]);
         float2* dst = Y + (int64_t)col * ldy + row0 + tr;
-        if (keep) {
-            if (BMODE == 1) cfma(out, beta, *dst);
-            *dst = out;
-        }
-    }
-}
-
-// ---- forward product over a 64-column row-major panel, the panel rows of a RUN of 16 matrix rows loaded ONCE, results in REGISTERS ----
-// k_csrmm_gather_tile64 loads the panel row of every nonzero: 5e7 x 512 bytes through the vector memory path for a gridding matrix
-// whose 16 consecutive samples (half a grid cell apart along a spoke) touch ~100 DISTINCT panel rows with their 432 nonzeros, and
-// that path -- ~25-30 bytes per clock and CU for 16-byte-per-lane gathers -- is what bounds it (profiles/r04_cfg3_forward_notes.txt:
-// neither whole-line loads, nor software pipelining, nor folding the panel into the L1 moved it).  Here the host groups the
-// nonzeros of a run of 16 rows by panel row (ig_csr_runs_build): a wave walks the run's distinct panel rows -- lane = panel column,
-// ONE 512-byte load per panel row, eight rows in flight in a ring of registers -- and adds w * row into the result rows of the
-// samples that use it.  A first version kept those 16 result rows in LDS (read-add-write per entry): 7.5-10 instructions per entry,
-// issue-bound at the old kernel's time.  The results now sit in REGISTERS (lane = column: 16 rows x (re, im) = v[128..159]) addressed
-// through the VGPR index mode -- an entry's row is wave-uniform, so its multiply-adds name v128 / v129 with M0 = {destination and
-// third source relative, 2 row}: 2 v_readlane + s_mov m0 + 2 v_fma per real-weight entry, no LDS traffic, no read-modify-write
-// chain through memory (the technique of k_bricks_wide64r).  The compiler never sees those registers: it is capped at 96 VGPRs
-// (amdgpu_num_vgpr), the kernel claims 160, and every access to v96..v159 is an assembly block with literal register numbers.
-//   dcols[j]   : panel row (compact column of the matrix) | (number of its entries - 1) << 27, the run's distinct rows in turn
-//   entries[e] : {row of the run 0..15, re, im}, grouped by distinct panel row in the order of dcols; a run's entries sit at
-//                rowptr[16 run] .. rowptr[16 (run + 1)) like its nonzeros in the CSR
-constexpr int RUN_ROWS = 16;
-struct RunEntry { uint32_t row; float re, im; };
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for_runs(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for_runs<I + 1, N>(f);
-    }
-}
-template <int K, int END>
-__device__ __forceinline__ void runs_acc_zero() {
-    if constexpr (K < END) {
-        asm volatile("v_mov_b64 v[%0:%1], 0" :: "i"(96 + 2 * K), "i"(97 + 2 * K));
-        runs_acc_zero<K + 1, END>();
-    }
-}
-template <int K, int END>
-__device__ __forceinline__ void runs_acc_store(float2* __restrict__ dst /* + K * TLD */, int tld) {
-    if constexpr (K < END) {
-        float re, im;
-        asm volatile("v_mov_b32 %0, v[%2]\n\tv_mov_b32 %1, v[%3]" : "=v"(re), "=v"(im) : "i"(96 + 2 * K), "i"(97 + 2 * K));
-        dst[K * tld] = make_float2(re, im);
-        runs_acc_store<K + 1, END>(dst, tld);
-    }
-}
-
-template <int BMODE, bool REALW>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(56)))
-k_csrmm_runs64r(int64_t M, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ run_dptr, const uint32_t* __restrict__ dcols,
-                const RunEntry* __restrict__ entries, const int32_t* __restrict__ run_order /* optional: the runs in the order to process them */,
-                const float2* __restrict__ X /* [row][64] */, float2* __restrict__ Y, int64_t ldy, float2 alpha, float2 beta) {
-    constexpr int TLD = 65;
-    __shared__ float2 tile[64 * TLD];
-    asm volatile("" ::: "v127");                          // the kernel owns 128 VGPRs: v0..v55 the compiler's, v56..v59 the prefetched
-                                                          // windows, v64..v95 a ring of 16 panel rows, v96..v127 the run's 16 result rows
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // What bounds the kernel is the bytes its panel rows cost in HBM (the loads alone take 1.40 of its 1.58 ms), and a panel row is
-    // wanted by ~2.3 runs: runs that are neighbours in SPACE should run close in time behind one L2.  The host may hand over an
-    // order of the runs (by the grid brick they start in); every XCD walks a contiguous range of it (blocks are dealt round-robin
-    // to the XCDs otherwise).  A run's 16 result rows are whole 128-byte lines of the column-major result, so any order stores
-    // full lines.
-    const int64_t blk = xcd_block(blockIdx.x, gridDim.x);
-    const int64_t nruns = (M + RUN_ROWS - 1) / RUN_ROWS;
-    const int64_t slot = blk * 4 + wv;
-    const int64_t run = slot < nruns ? (run_order ? (int64_t)run_order[slot] : slot) : nruns;
-    asm volatile("s_set_gpr_idx_on %0, 0x0" :: "s"(0));   // index mode on for the whole kernel; M0 = 0: nothing relative
-    runs_acc_zero<0, RUN_ROWS>();
-    if (run < nruns) {
-        const int32_t d0 = run_dptr[run], nd = run_dptr[run + 1] - d0;
-        const int64_t rlo = run * RUN_ROWS, rhi = rlo + RUN_ROWS < M ? rlo + RUN_ROWS : M;
-        const int32_t e0 = rowptr[rlo], ne = rowptr[rhi] - e0;
-        const rsrc_t r_d = make_rsrc(dcols + d0), r_e = make_rsrc(entries + e0);
-        // the repacked panel may exceed 2 GB (config 3: 2.57 GB): a descriptor over the whole 4 GB offset range.  Rows past the run's
-        // end are requested all the same (row 0: the load counts, so the waits below stay static)
-        const rsrc_t r_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float2*>(X), 0, -1, 0x00020000);
-        const unsigned x_voff = (unsigned)lane * 8u;
-        // Windows of 64 distinct rows / 64 entries, one per lane, handed out with v_readlane (wave-uniform control).  Inside the loop
-        // EVERY load is an assembly block: one load the compiler knows about makes its wait-count pass drain the whole ring in front
-        // of each use of the window registers (s_waitcnt vmcnt(0) at the head of every row: 3.5 ms).  The next windows are
-        // prefetched into v112..v114 (entries) and v115 (distinct rows) and moved over when the current ones are used up.
-        int32_t dbase = 0, ebase = 0;
-        uint32_t dv = (uint32_t)buf_ld_i32(r_d, lane < nd ? (unsigned)lane * 4u : IG_OOB);
-        struct Win { uint32_t m0w; float re, im; };
-        auto cook = [&](u3 raw) { Win wn; wn.m0w = ((raw.x & 15u) * 2u) | 0xC000u; wn.re = __uint_as_float(raw.y); wn.im = __uint_as_float(raw.z); return wn; };
-        Win ev = cook(buf_ld_u3(r_e, lane < ne ? (unsigned)lane * 12u : IG_OOB));
-        auto prefetch_entries = [&](int32_t base) __attribute__((always_inline)) {     // entries base .. base + 63 -> v112..v114
-            const unsigned o = base + lane < ne ? (unsigned)(base + lane) * 12u : IG_OOB;
-            const rsrc_t re_ = r_e;
-            asm volatile("buffer_load_dwordx3 v[56:58], %0, %1, 0 offen" :: "v"(o), "s"(re_) : "memory");
-        };
-        auto prefetch_rows = [&](int32_t base) __attribute__((always_inline)) {        // distinct rows base .. base + 63 -> v115
-            const unsigned o = base + lane < nd ? (unsigned)(base + lane) * 4u : IG_OOB;
-            const rsrc_t rd_ = r_d;
-            asm volatile("buffer_load_dword v59, %0, %1, 0 offen" :: "v"(o), "s"(rd_) : "memory");
-        };
-        auto take_entries = [&]() __attribute__((always_inline)) -> Win {
-            u3 raw;
-            asm volatile("v_mov_b32 %0, v56\n\tv_mov_b32 %1, v57\n\tv_mov_b32 %2, v58" : "=v"(raw.x), "=v"(raw.y), "=v"(raw.z));
-            return cook(raw);
-        };
-        prefetch_entries(64);
-        prefetch_rows(64);
-        int32_t ei = 0;                                   // next entry inside the window `ev`
-        int32_t since = 0;                                // panel rows requested since the entry window in flight was asked for
-        // panel row j of the run -> ring slot KF (v[64 + 2 KF], v[65 + 2 KF]); returns the row's word (column | (entries - 1) << 27)
-        auto request = [&](auto kf, int32_t j) __attribute__((always_inline)) -> uint32_t {
-            constexpr int KF = decltype(kf)::value;
-            const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)dv, (j - dbase) & 63);
-            const uint32_t o = j < nd ? (w & 0x7ffffffu) * 512u : 0u;       // (past the run's end: panel row 0 once more -- a hit in the L1)
-            const rsrc_t rx = r_x;
-            const unsigned vo = x_voff;
-            asm volatile("s_nop 4\n\tbuffer_load_dwordx2 v[%0:%1], %2, %3, %4 offen" :: "i"(64 + 2 * KF), "i"(65 + 2 * KF), "v"(vo), "s"(rx), "s"(o) : "memory");
-            ++since;
-            return w;
-        };
-        // acc[row] += w * x for ONE entry: M0 = {third source and destination relative, 2 row}
-#define IG_RUNS_MAC_R(M, WR)      "s_mov_b32 m0, " M "\n\ts_nop 0\n\tv_fma_f32 v96, " WR ", v[%[xr]], v96\n\tv_fma_f32 v97, " WR ", v[%[xi]], v97\n\t"
-#define IG_RUNS_MAC_C(M, WR, WI)  IG_RUNS_MAC_R(M, WR) "v_fma_f32 v96, -" WI ", v[%[xi]], v96\n\tv_fma_f32 v97, " WI ", v[%[xr]], v97\n\t"
-        auto consume = [&](auto kf, uint32_t w, int32_t j) __attribute__((always_inline)) {
-            constexpr int KF = decltype(kf)::value;
-            if (j >= nd) return;
-            int cnt = (int)(w >> 27) + 1;
-            // this row has arrived: fifteen younger panel-row loads may still be out (anything else in flight is younger than they are
-            // or older than this row; loads return in order)
-            asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
-            while (cnt > 0) {
-                if (ei >= 64) {                           // the window of entries is used up: the prefetched one takes over
-                    // it was asked for a window ago: once sixteen panel rows have been requested since, the vmcnt(15) above has
-                    // covered it (in-order return); a run of very dense rows gets there sooner and waits for everything
-                    if (since < 16) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    ev = take_entries(); ebase += 64; ei = 0;
-                    prefetch_entries(ebase + 64);
-                    since = 0;
-                    // (that load is younger than every panel row in flight: the static waits stay valid, only stricter)
-                }
-                const int avail = 64 - ei;
-                if (cnt >= 4 && avail >= 4) {
-                    uint32_t m[4]; float a[4], bi[4];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        m[q] = (uint32_t)__builtin_amdgcn_readlane((int)ev.m0w, ei + q);
-                        a[q] = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(ev.re), ei + q));
-                        if (!REALW) bi[q] = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(ev.im), ei + q));
-                    }
-                    if (REALW)
-                        asm volatile(IG_RUNS_MAC_R("%0", "%4") IG_RUNS_MAC_R("%1", "%5") IG_RUNS_MAC_R("%2", "%6") IG_RUNS_MAC_R("%3", "%7") "s_mov_b32 m0, 0"
-                                     :: "s"(m[0]), "s"(m[1]), "s"(m[2]), "s"(m[3]), "s"(a[0]), "s"(a[1]), "s"(a[2]), "s"(a[3]),
-                                        [xr] "i"(64 + 2 * KF), [xi] "i"(65 + 2 * KF) : "memory");
-                    else
-                        asm volatile(IG_RUNS_MAC_C("%0", "%4", "%8") IG_RUNS_MAC_C("%1", "%5", "%9") IG_RUNS_MAC_C("%2", "%6", "%10") IG_RUNS_MAC_C("%3", "%7", "%11") "s_mov_b32 m0, 0"
-                                     :: "s"(m[0]), "s"(m[1]), "s"(m[2]), "s"(m[3]), "s"(a[0]), "s"(a[1]), "s"(a[2]), "s"(a[3]),
-                                        "s"(bi[0]), "s"(bi[1]), "s"(bi[2]), "s"(bi[3]), [xr] "i"(64 + 2 * KF), [xi] "i"(65 + 2 * KF) : "memory");
-                    ei += 4; cnt -= 4;
-                } else {
-                    const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)ev.m0w, ei);
-                    const float a = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(ev.re), ei));
-                    if (REALW) {
-                        asm volatile(IG_RUNS_MAC_R("%0", "%1") "s_mov_b32 m0, 0" :: "s"(m), "s"(a), [xr] "i"(64 + 2 * KF), [xi] "i"(65 + 2 * KF) : "memory");
-                    } else {
-                        const float bi = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(ev.im), ei));
-                        asm volatile(IG_RUNS_MAC_C("%0", "%1", "%2") "s_mov_b32 m0, 0" :: "s"(m), "s"(a), "s"(bi), [xr] "i"(64 + 2 * KF), [xi] "i"(65 + 2 * KF) : "memory");
-                    }
-                    ei += 1; cnt -= 1;
-                }
-            }
-        };
-#undef IG_RUNS_MAC_C
-#undef IG_RUNS_MAC_R
-        // ring of sixteen: rows d .. d + 15 in flight while row d is consumed; slot KF is refilled (row d + 16) right after its row is
-        // used up.  (What bounds the kernel is bytes in flight: with eight rows per wave and three waves per SIMD -- 48 KB per CU --
-        // it fetched its 5.9 GB at 3.2 TB/s, 1.87 ms, the per-nonzero gather's time.)
-        uint32_t wr_[16];
-        auto fill = [&](auto k) __attribute__((always_inline)) { wr_[decltype(k)::value] = request(k, decltype(k)::value); };
-        static_for_runs<0, 16>(fill);
-        for (int32_t d = 0; d < nd; d += 16) {
-            const int32_t dn = d + 16;
-            const bool move = dn < nd && ((dn - dbase) & 63) == 0;
-            auto step = [&](auto k) __attribute__((always_inline)) {
-                constexpr int KF = decltype(k)::value;
-                consume(k, wr_[KF], d + KF);
-                if (KF == 0 && move) {                    // (the next window was asked for 64 rows ago: the vmcnt(15) above covers it)
-                    asm volatile("v_mov_b32 %0, v59" : "=v"(dv));
-                    dbase = dn;
-                    prefetch_rows(dn + 64);
-                }
-                wr_[KF] = request(k, dn + KF);
-            };
-            static_for_runs<0, 16>(step);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the out-of-range tail requests write the ring registers too)
-    }
-    asm volatile("s_set_gpr_idx_off");
-    if (run >= nruns) return;
-    // the run's results: registers -> the wave's quarter of the tile -> full 128-byte lines of the column-major result (lanes = 16
-    // rows x 4 columns).  Only this wave touches its quarter: LDS operations of a wave execute in order, the fence pins that for
-    // the compiler.
-    float2* __restrict__ mine = tile + (wv * RUN_ROWS) * TLD;
-    runs_acc_store<0, RUN_ROWS>(mine + lane, TLD);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const int r16 = lane & 15, cg = lane >> 4;
-    const int64_t orow = run * RUN_ROWS + r16;
-    const bool keep = orow < M;
-#pragma unroll 4
-    for (int i = 0; i < 16; ++i) {
-        const int col = cg + 4 * i;
-        float2 out = cmul(alpha, mine[r16 * TLD + col]);
-        float2* dst = Y + (int64_t)col * ldy + orow;
         if (keep) {
             if (BMODE == 1) cfma(out, beta, *dst);
             *dst = out;
@@ -1232,6 +1005,49 @@ k_pack_panel_tiled(int64_t rows, int64_t N, const float2* __restrict__ X, int64_
     }
 }
 
+}  // namespace
+
+int ig_pack_panel(ig_ctx* ctx, int64_t rows, int64_t N, int np, const float2* X, int64_t ldx, const int32_t* xperm,
+                  bool may_decline, const float2** packed) {
+    *packed = nullptr;
+    const size_t need = (size_t)rows * np * 8;
+    // The repack buffer is a per-context scratch that only grows (reported by ig_mem_info, not by the caller's own
+    // accounting): a caller that can also run unpacked (slower, same result) takes it only while it is at most a quarter
+    // of the free device memory, and does without if the allocation fails.
+    if (may_decline && (need == 0 || need > ((size_t)16 << 30))) return IG_OK;
+    if (ctx->xpack_bytes < need) {
+        if (may_decline) {
+            size_t free_b = 0, total_b = 0;
+            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
+            if (need > (free_b + ctx->xpack_bytes) / 4) return IG_OK;
+        }
+        if (ctx->d_xpack) { IG_HIP(ctx, hipStreamSynchronize(ctx->stream)); IG_HIP(ctx, hipFree(ctx->d_xpack)); ctx->d_xpack = nullptr; ctx->xpack_bytes = 0; }
+        if (!may_decline) {
+            IG_HIP(ctx, hipMalloc((void**)&ctx->d_xpack, need));
+        } else if (hipMalloc((void**)&ctx->d_xpack, need) != hipSuccess) { (void)hipGetLastError(); ctx->d_xpack = nullptr; return IG_OK; }
+        ctx->xpack_bytes = need;
+    }
+    ig_prof_scope prof(ctx, "pack_panel", (double)rows * N * 8.0 + (double)need);
+    float2* xp = (float2*)ctx->d_xpack;
+    const int64_t cap = (int64_t)ctx->num_cu * 16;
+    int64_t g = np <= 8 ? (rows * np + BLK - 1) / BLK : (rows + 63) / 64;          // the tiled kernel: 64 panel rows per workgroup
+    if (g > cap) g = cap;
+#define IG_PACK(KERNEL_) hipLaunchKernelGGL(KERNEL_, dim3((unsigned)g), dim3(BLK), 0, ctx->stream, rows, N, X, ldx, xp, xperm)
+    if (np == 1)       IG_PACK(k_pack_panel<1>);
+    else if (np == 2)  IG_PACK(k_pack_panel<2>);
+    else if (np == 4)  IG_PACK(k_pack_panel<4>);
+    else if (np == 8)  IG_PACK(k_pack_panel<8>);
+    else if (np == 16) IG_PACK(k_pack_panel_tiled<16>);
+    else if (np == 32) IG_PACK(k_pack_panel_tiled<32>);
+    else               IG_PACK(k_pack_panel_tiled<64>);
+#undef IG_PACK
+    IG_LAUNCH_CHECK(ctx, "k_pack_panel");
+    *packed = xp;
+    return IG_OK;
+}
+
+namespace {
+
 // ---- brick-binned adjoint gridding ------------------------------------------------------------------------------
 // Y_il = alpha * G^H X for a gridding matrix G (rows = k-space samples, ~27 taps each, columns = grid points numbered
 // kx + n0*(km + nm*ks)) -- the SCATTER view, made race-free by binning.  The grid is cut into bricks of 16 x BM x BS cells.
@@ -1251,9 +1067,6 @@ k_pack_panel_tiled(int64_t rows, int64_t N, const float2* __restrict__ X, int64_
 // walked through pairs -> rowptr -> colind/vals (6.7 ms: dependent loads at 8 waves per CU); a workgroup per brick with LDS
 // float atomics (5.4 ms: ds_add_f32 retires about one lane every four clocks); a wave per brick, every lane loading its own
 // copy of the entry and the X value (1.60 ms); runs of bricks (1.31 ms); the form below (0.91 ms).
-struct BrickTask { int32_t lo, hi, bt, nb_flags; };     // entries [lo, hi) = bricks table[bt .. bt + (nb_flags & 0xffff)); bit 16: shared
-struct BrickRef { int32_t brick, end; };                  // a non-empty brick and where its entries end
-struct BrickEntry { uint32_t cell; float re, im; };       // 12 bytes; cell == 0xffffffff: padding
 
 // One wave per task.  A task is a run of consecutive non-empty bricks (a few thousand entries, at most 64 bricks and
 // 512 segments) or a piece of one heavy brick (shared).  The wave keeps ONE brick image in LDS and walks the run in
@@ -1617,377 +1430,6 @@ k_grid_slots(const BrickTask* __restrict__ tasks, int ntasks, const BrickRef* __
     flush();
 }
 
-// ---- the same scatter for a 64-column panel at the reference boundary (column-major Y) -----------------------------
-// Y(K x 64, column-major) = alpha * A^H X for any CSR whose K is a multiple of 16: bricks of 16 consecutive rows of Y,
-// 12-byte entries {row of Y inside the brick, re, im} in brick order plus the row of X of every entry (no padding: a round
-// is ONE entry, the 64 lanes are the 64 columns).  Entries and rows arrive through the scalar cache (wave-uniform
-// addresses: s_load; rows three groups of four ahead, payloads one), the packed X row of an entry is one 512-byte wave
-// load at a scalar offset (two groups ahead), the brick image [16][64 (+1)] sits in LDS, and a finished brick goes out as
-// full 128-byte lines (lanes = 16 rows x 4 columns).  Y is zeroed first (beta == 0: rows no nonzero touches are zero);
-// pieces of heavy bricks add with float atomics.
-constexpr int WIDE_LD = 65;                 // image row stride in float2: conflict-free both as [cell][lane] and transposed
-
-__global__ void __launch_bounds__(BLK)
-k_bricks_wide64(const BrickTask* __restrict__ tasks, int ntasks, const BrickRef* __restrict__ btab,
-                const BrickEntry* __restrict__ entries, const uint32_t* __restrict__ entry_rows,
-                const float2* __restrict__ Xp /* [row][64] */,
-                float2* __restrict__ Y, int64_t ldy, float2 alpha) {
-    __shared__ float2 acc_all[WAVES_PER_BLOCK * 16 * WIDE_LD];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int blk = (int)blockIdx.x;
-    const int task = blk * WAVES_PER_BLOCK + wv;
-    if (blk >= (int)gridDim.x || task >= ntasks) return;
-    const BrickTask tk = tasks[task];
-    const int nb = tk.nb_flags & 0xffff;
-    const bool shared = (tk.nb_flags >> 16) & 1;
-    const int32_t nent = tk.hi - tk.lo;
-    float2* __restrict__ acc = acc_all + wv * 16 * WIDE_LD;
-    const BrickEntry* __restrict__ en = entries + tk.lo;
-    const uint32_t* __restrict__ er = entry_rows + tk.lo;
-    const rsrc_t r_x = make_rsrc(Xp);
-
-    struct Pay { BrickEntry e[4]; };
-    struct Rows { uint32_t r[4]; };
-    Pay pa, pb, pc;
-    Rows ra, rb, rc;
-    float2 xa[4], xb[4], xc[4];
-    auto fetch_rows = [&](Rows& g, int gi) {             // wave-uniform addresses: scalar loads
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { const int32_t idx = gi * 4 + i; g.r[i] = er[idx < nent ? idx : nent - 1]; }
-    };
-    auto fetch_pay = [&](Pay& g, int gi) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { const int32_t idx = gi * 4 + i; g.e[i] = en[idx < nent ? idx : nent - 1]; }
-    };
-    auto request = [&](float2* x, const Rows& g, int gi) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            x[i] = buf_ld<false>(r_x, gi * 4 + i < nent ? (unsigned)lane * 8u : IG_OOB, g.r[i] * 512u);
-    };
-    fetch_rows(ra, 0);
-    fetch_rows(rb, 1);
-    fetch_rows(rc, 2);
-    fetch_pay(pa, 0);
-    const float2 my_ref = buf_ld<false>(make_rsrc(btab + tk.bt), lane < nb ? (unsigned)lane * 8u : IG_OOB, 0);
-    for (int e = lane; e < 16 * WIDE_LD; e += 64) acc[e] = make_float2(0.f, 0.f);
-    request(xa, ra, 0);
-    request(xb, rb, 1);
-    int my_end = 0x7fffffff;
-    if (lane < nb && !shared) my_end = (int)__float_as_uint(my_ref.y) - tk.lo;
-    const int my_row0 = (int)__float_as_uint(my_ref.x) * 16;
-
-    int cur = 0;
-    int32_t cur_end = __builtin_amdgcn_readlane(my_end, 0);
-    auto flush = [&]() {
-        const int row0 = __builtin_amdgcn_readlane(my_row0, cur);
-        const int cell = lane & 15, cg = lane >> 4;
-#pragma unroll 4
-        for (int i = 0; i < 16; ++i) {
-            const int col = cg + 4 * i;
-            float2* a = acc + cell * WIDE_LD + col;
-            const float2 o = cmul(alpha, *a);
-            float2* dst = Y + (int64_t)col * ldy + row0 + cell;           // 16 lanes = one 128-byte line of column `col`
-            if (shared) {
-                asm volatile("global_atomic_add_f32 %0, %1, off\n\tglobal_atomic_add_f32 %0, %2, off offset:4"
-                             :: "v"(dst), "v"(o.x), "v"(o.y) : "memory");
-            } else {
-                asm volatile("global_store_dwordx2 %0, %1, off" :: "v"(dst), "v"(o) : "memory");
-            }
-            *a = make_float2(0.f, 0.f);
-        }
-        ++cur;
-        cur_end = __builtin_amdgcn_readlane(my_end, cur & 63);
-    };
-    // group gi: request the X rows of group gi + 2, fetch the rows of gi + 3 and the payloads of gi + 1, accumulate gi
-    auto body = [&](const Pay& p, Pay& pnext, const float2* x, float2* x2, const Rows& r2, Rows& r3, int gi) {
-        request(x2, r2, gi + 2);
-        fetch_rows(r3, gi + 3);
-        fetch_pay(pnext, gi + 1);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int32_t idx = gi * 4 + i;
-            if (idx < nent) {
-                if (idx >= cur_end) flush();
-                const float vr = p.e[i].re, vi = p.e[i].im;
-                float2* a = acc + (int)p.e[i].cell * WIDE_LD + lane;
-                float2 t = *a;
-                t.x += fmaf(vr, x[i].x, vi * x[i].y);                     // conj(v) * x
-                t.y += fmaf(vr, x[i].y, -vi * x[i].x);
-                *a = t;
-            }
-        }
-    };
-    const int ngroup = (nent + 3) / 4;
-    for (int gi = 0; gi < ngroup; gi += 3) {             // (groups past the end do nothing: no early exit, see k_grid_bricks)
-        body(pa, pb, xa, xc, rc, ra, gi);
-        body(pb, pc, xb, xa, ra, rb, gi + 1);
-        body(pc, pa, xc, xb, rb, rc, gi + 2);
-    }
-    flush();
-}
-
-// The same scatter with the brick image in REGISTERS (round 3).  The 16-row bricks above fetch a row of X once per ENTRY
-// (the L1 serves the repeats: 16 tag look-ups per 512-byte wave load, 1.0 G of them per launch) and once per (sample, brick)
-// group from HBM -- ten groups per sample for a 27-tap gridding kernel, 9.7 GB of the launch's 15.6.  Bigger bricks need fewer
-// groups (16 x 2 x 2 grid points: 4.5 per sample) but 33 KB of LDS per wave.  Here
-//   * lane c keeps column c of the whole brick in 128 VGPRs (v[128 + 2 cell] = re, v[129 + 2 cell] = im), and because the cell
-//     of an entry is wave-uniform the accumulation addresses them through the VGPR index mode: M0 = {third source and
-//     destination relative, index 2 cell}, four multiply-adds per entry, no LDS traffic, no read-after-write through memory;
-//   * entries come in QUADS: a sample's share of a brick is padded to a multiple of four (ig_grid_bricks_fill, unit 4; the
-//     padding repeats a real cell with weight zero) and ONE panel row is loaded per quad -- 13 M wave loads instead of 50 M;
-//     brick boundaries fall between quads.
-// How it is written:
-//   * The compiler never sees the image or the panel rows: the kernel caps its own allocation at v0..v71 (amdgpu_num_vgpr),
-//     v72..v79 hold two trips of entries in flight, v80..v103 twelve panel rows, and every access to v72..v255 is an
-//     assembly block with literal register numbers.  (Handing the image to the compiler as four 32-register operands made it
-//     copy whole tuples at every join of the control flow; leaving the loads to it kept one group in flight.)
-//   * Loads return in order, so "at most 11 younger loads outstanding" means the row about to be used has arrived, whatever
-//     else -- the trips' loads, the stores of a flush -- is in flight.
-//   * The index mode is switched on ONCE, with no operand relative (M0[15:12] = 0: the compiler's code runs unchanged; it never
-//     writes M0 in this kernel); a block that addresses the image writes M0 itself and clears it again.
-//   * Entries do not come through the scalar cache (at the eight waves per CU that 256 registers allow, every miss stalled a
-//     wave for a trip to HBM): lane e of the wave loads entry e of a TRIP of 48 (12 quads), two trips ahead; wave-uniform
-//     values are read out with v_readlane (constant lane numbers) when their turn comes.  The rows sit in a second stream
-//     shifted by the look-ahead of 11 quads, so quad k of a trip requests with lane k.
-//   * A wave issues one instruction per four clocks whatever its kind, and two waves per SIMD hide little: the loop is
-//     written for instruction count.
-// The flush goes tile by tile (16 rows of Y) through the [16][65] LDS image of the kernel above, full lines out.
-template <int K, int END>
-__device__ __forceinline__ void wide_img_zero() {
-    if constexpr (K < END) {
-        asm volatile("v_mov_b64 v[%0:%1], 0" :: "i"(128 + 2 * K), "i"(129 + 2 * K));
-        wide_img_zero<K + 1, END>();
-    }
-}
-
-// REALW: 8-byte entries {cell, re} of a matrix whose weights are all real (a plain gridding matrix): a third less of the format to read,
-// two v_readlane and two multiply-adds less per entry.
-template <int NT /* 16-row tiles per brick: bm * bs = 2, 4 */, bool REALW = false>
-__global__ void __launch_bounds__(BLK) __attribute__((amdgpu_num_vgpr(72)))
-k_bricks_wide64r(const BrickTask* __restrict__ tasks, int ntasks, const BrickRef* __restrict__ btab,
-                 const BrickEntry* __restrict__ entries, const uint32_t* __restrict__ quad_rows,
-                 const float2* __restrict__ Xp /* [row][64] */, float2* __restrict__ Y, int64_t ldy, float2 alpha,
-                 int n0, int nm, int bm_log2, int bs_log2, int nbx, int nbm) {
-    __shared__ float2 acc_all[WAVES_PER_BLOCK * 16 * WIDE_LD];
-    asm volatile("" ::: "v255");                          // the kernel owns 256 VGPRs
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int blk = (int)blockIdx.x;
-    const int task = blk * WAVES_PER_BLOCK + wv;
-    if (blk >= (int)gridDim.x || task >= ntasks) return;
-    const BrickTask tk = tasks[task];
-    const int nb = tk.nb_flags & 0xffff;
-    const bool shared = (tk.nb_flags >> 16) & 1;
-    const int32_t nent = tk.hi - tk.lo;                   // a multiple of 4
-    const int32_t nquad = nent >> 2;
-    float2* __restrict__ acc = acc_all + wv * 16 * WIDE_LD;
-    asm volatile("s_set_gpr_idx_on %0, 0x0" :: "s"(0));
-    rsrc_t r_en = REALW ? make_rsrc(reinterpret_cast<const float2*>(entries) + tk.lo) : make_rsrc(entries + tk.lo);   // (not const: operands of assembly blocks inside generic lambdas)
-    rsrc_t r_qr = make_rsrc(quad_rows + (tk.lo >> 2));
-    rsrc_t r_x = make_rsrc(Xp);
-
-    constexpr int TRIP = 48, TQ = TRIP / 4;               // entries / quads per trip
-    constexpr int AHEAD = TQ - 1;                         // a panel row is requested 11 quads before its entries are used
-    struct Trip { uint32_t m0w; float re, im; uint32_t rowoff; };             // lane e: entry e; lane q: the row of quad q + AHEAD
-    // raw trips in flight: slot A = v[72:75], slot B = v[76:79]
-    auto load_raw = [&](auto slot, int ti) __attribute__((always_inline)) {
-        constexpr int R = 72 + 4 * decltype(slot)::value;
-        const int32_t e = ti * TRIP + lane, q = ti * TQ + lane + AHEAD;
-        const unsigned oe = (lane < TRIP && e < nent) ? (unsigned)e * (REALW ? 8u : 12u) : IG_OOB;
-        const unsigned oq = (lane < TQ && q < nquad) ? (unsigned)q * 4u : IG_OOB;           // (past the end: row 0, never used)
-        const rsrc_t ren = r_en, rqr = r_qr;             // (copies: a generic lambda does not capture a variable only an asm operand names)
-        if (REALW)
-            asm volatile("buffer_load_dwordx2 v[%0:%1], %3, %4, 0 offen\n\t"
-                         "buffer_load_dword v[%2], %5, %6, 0 offen"
-                         :: "i"(R), "i"(R + 1), "i"(R + 3), "v"(oe), "s"(ren), "v"(oq), "s"(rqr) : "memory");
-        else
-            asm volatile("buffer_load_dwordx3 v[%0:%1], %3, %4, 0 offen\n\t"
-                         "buffer_load_dword v[%2], %5, %6, 0 offen"
-                         :: "i"(R), "i"(R + 2), "i"(R + 3), "v"(oe), "s"(ren), "v"(oq), "s"(rqr) : "memory");
-    };
-    auto cook_a = [&]() __attribute__((always_inline)) {                        // slot A -> the words the loop reads with v_readlane
-        uint32_t c, re, im, row;
-        asm volatile("v_mov_b32 %0, v72\n\tv_mov_b32 %1, v73\n\tv_mov_b32 %2, v74\n\tv_mov_b32 %3, v75" : "=v"(c), "=v"(re), "=v"(im), "=v"(row));
-        Trip t;
-        t.m0w = ((c & (16u * NT - 1u)) * 2u) | 0xC000u;                       // M0: third source and destination relative, index 2 cell
-        t.re = __uint_as_float(re); t.im = __uint_as_float(im);
-        t.rowoff = row * 512u;
-        return t;
-    };
-    load_raw(std::integral_constant<int, 0>{}, 0);
-    load_raw(std::integral_constant<int, 1>{}, 1);
-    const float2 my_ref = buf_ld<false>(make_rsrc(btab + tk.bt), lane < nb ? (unsigned)lane * 8u : IG_OOB, 0);
-    wide_img_zero<0, 16 * NT>();
-    const unsigned x_voff = (unsigned)lane * 8u;
-    // the panel row whose byte offset sits in lane `ql` of `src` -> buffer KF (v[80 + 2 KF], v[81 + 2 KF])
-    auto request = [&](auto kf, auto ql, uint32_t src) __attribute__((always_inline)) {
-        constexpr int KF = decltype(kf)::value;
-        const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)src, decltype(ql)::value);
-        const rsrc_t rx = r_x;
-        const unsigned vo = x_voff;
-        // (s_nop: five wait states between a VALU writing an SGPR and a memory instruction reading it)
-        asm volatile("s_nop 4\n\tbuffer_load_dwordx2 v[%0:%1], %2, %3, %4 offen" :: "i"(80 + 2 * KF), "i"(81 + 2 * KF), "v"(vo), "s"(rx), "s"(o) : "memory");
-    };
-    // quads 0 .. 10: their rows are not in the shifted stream
-    {
-        const uint32_t first = (uint32_t)buf_ld_i32(r_qr, (lane < AHEAD && lane < nquad) ? (unsigned)lane * 4u : IG_OOB) * 512u;
-        auto pro = [&](auto k) __attribute__((always_inline)) { request(k, k, first); };
-        pro(std::integral_constant<int, 0>{}); pro(std::integral_constant<int, 1>{}); pro(std::integral_constant<int, 2>{});
-        pro(std::integral_constant<int, 3>{}); pro(std::integral_constant<int, 4>{}); pro(std::integral_constant<int, 5>{});
-        pro(std::integral_constant<int, 6>{}); pro(std::integral_constant<int, 7>{}); pro(std::integral_constant<int, 8>{});
-        pro(std::integral_constant<int, 9>{}); pro(std::integral_constant<int, 10>{});
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    Trip tc = cook_a();
-    asm volatile("v_mov_b32 v72, v76\n\tv_mov_b32 v73, v77\n\tv_mov_b32 v74, v78\n\tv_mov_b32 v75, v79" ::: "memory");
-    Trip tn = cook_a();
-    load_raw(std::integral_constant<int, 0>{}, 2);
-    load_raw(std::integral_constant<int, 1>{}, 3);
-    int my_end = 0x7fffffff;
-    if (lane < nb && !shared) my_end = (int)__float_as_uint(my_ref.y) - tk.lo;
-    int my_row0;                                          // first row of Y of the brick's tile (0, 0)
-    {
-        const int b = (int)__float_as_uint(my_ref.x);
-        const int bx = b % nbx, bmi = (b / nbx) % nbm, bsi = b / (nbx * nbm);
-        my_row0 = bx * 16 + n0 * ((bmi << bm_log2) + nm * (bsi << bs_log2));
-    }
-    const int tile_cell = lane & 15, tile_cg = lane >> 4;
-
-    int cur = 0;
-    int32_t cur_end = __builtin_amdgcn_readlane(my_end, 0);
-    auto tile_out = [&](int q, int row00) __attribute__((always_inline)) {       // the LDS image (tile q of the brick) -> Y
-        const int row0 = row00 + n0 * ((q & ((1 << bm_log2) - 1)) + nm * (q >> bm_log2));
-#pragma unroll 4
-        for (int i = 0; i < 16; ++i) {
-            const int col = tile_cg + 4 * i;
-            const float2 o = cmul(alpha, acc[tile_cell * WIDE_LD + col]);
-            float2* dst = Y + (int64_t)col * ldy + row0 + tile_cell;        // 16 lanes = one 128-byte line of column `col`
-            if (shared) {
-                asm volatile("global_atomic_add_f32 %0, %1, off\n\tglobal_atomic_add_f32 %0, %2, off offset:4"
-                             :: "v"(dst), "v"(o.x), "v"(o.y) : "memory");
-            } else {
-                asm volatile("global_store_dwordx2 %0, %1, off" :: "v"(dst), "v"(o) : "memory");
-            }
-        }
-    };
-    auto flush = [&]() __attribute__((always_inline)) {
-        const int row00 = __builtin_amdgcn_readlane(my_row0, cur);
-#pragma unroll 1
-        for (int q = 0; q < NT; ++q) {                   // a run-time loop: the kernel holds one flush site per quad of a trip
-            // tile q of the image (registers v[128 + 32 q ...]) -> LDS, read through the index mode (first source relative)
-            uint32_t any = 0;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                float t[16];
-                asm volatile("s_mov_b32 m0, %16\n\ts_nop 0\n\t"
-                             "v_mov_b32 %0, v128\n\tv_mov_b32 %1, v129\n\tv_mov_b32 %2, v130\n\tv_mov_b32 %3, v131\n\t"
-                             "v_mov_b32 %4, v132\n\tv_mov_b32 %5, v133\n\tv_mov_b32 %6, v134\n\tv_mov_b32 %7, v135\n\t"
-                             "v_mov_b32 %8, v136\n\tv_mov_b32 %9, v137\n\tv_mov_b32 %10, v138\n\tv_mov_b32 %11, v139\n\t"
-                             "v_mov_b32 %12, v140\n\tv_mov_b32 %13, v141\n\tv_mov_b32 %14, v142\n\tv_mov_b32 %15, v143\n\t"
-                             "s_mov_b32 m0, 0"
-                             : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3]), "=&v"(t[4]), "=&v"(t[5]), "=&v"(t[6]), "=&v"(t[7]),
-                               "=&v"(t[8]), "=&v"(t[9]), "=&v"(t[10]), "=&v"(t[11]), "=&v"(t[12]), "=&v"(t[13]), "=&v"(t[14]), "=&v"(t[15])
-                             : "s"((32 * q + 16 * h) | 0x1000));
-#pragma unroll
-                for (int c = 0; c < 8; ++c) acc[(8 * h + c) * WIDE_LD + lane] = make_float2(t[2 * c], t[2 * c + 1]);
-                if (shared) {
-#pragma unroll
-                    for (int c = 0; c < 16; ++c) any |= __float_as_uint(t[c]) << 1;       // (-0.0f counts as nothing)
-                }
-            }
-            if (shared && !__builtin_amdgcn_ballot_w64(any != 0)) continue;               // a piece that never touched this tile
-            tile_out(q, row00);
-        }
-        wide_img_zero<0, 16 * NT>();
-        ++cur;
-        cur_end = __builtin_amdgcn_readlane(my_end, cur & 63);
-    };
-    // quad k of the current trip (entries in lanes 4k .. 4k + 3, panel row in buffer k): request the row of the quad 11 ahead
-    // into the buffer the previous quad has just released, flush if a new brick starts here, accumulate.
-    auto body = [&](auto k, int32_t base) __attribute__((always_inline)) {
-        constexpr int KQ = decltype(k)::value;
-        request(std::integral_constant<int, (KQ + TQ - 1) % TQ>{}, k, tc.rowoff);
-        if (base >= nent) return;                                            // (trips are whole; the run is not)
-        if (base >= cur_end) flush();                                        // bricks are not empty: one flush
-        uint32_t mw[4]; float wr[4], wi[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            mw[i] = (uint32_t)__builtin_amdgcn_readlane((int)tc.m0w, 4 * KQ + i);
-            wr[i] = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(tc.re), 4 * KQ + i));
-            if (!REALW) wi[i] = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(tc.im), 4 * KQ + i));
-        }
-        if (REALW) {
-            // image[cell] += w * x, w real
-#define IG_WIDE_MAC_R(M, WR) \
-                     "s_mov_b32 m0, " M "\n\ts_nop 0\n\t" \
-                     "v_fma_f32 v128, " WR ", v[%8], v128\n\t" \
-                     "v_fma_f32 v129, " WR ", v[%9], v129\n\t"
-            asm volatile("s_waitcnt vmcnt(11)\n\t"                            // this quad's row has arrived
-                         IG_WIDE_MAC_R("%0", "%4") IG_WIDE_MAC_R("%1", "%5") IG_WIDE_MAC_R("%2", "%6") IG_WIDE_MAC_R("%3", "%7")
-                         "s_mov_b32 m0, 0"
-                         :: "s"(mw[0]), "s"(mw[1]), "s"(mw[2]), "s"(mw[3]), "s"(wr[0]), "s"(wr[1]), "s"(wr[2]), "s"(wr[3]),
-                            "i"(80 + 2 * KQ), "i"(81 + 2 * KQ) : "memory");
-#undef IG_WIDE_MAC_R
-            return;
-        }
-        // image[cell] += conj(v) * x for the quad's four entries (one panel row)
-#define IG_WIDE_MAC(M, WR, WI) \
-                     "s_mov_b32 m0, " M "\n\ts_nop 0\n\t" \
-                     "v_fma_f32 v128, " WR ", v[%12], v128\n\t" \
-                     "v_fma_f32 v129, " WR ", v[%13], v129\n\t" \
-                     "v_fma_f32 v128, " WI ", v[%13], v128\n\t" \
-                     "v_fma_f32 v129, -" WI ", v[%12], v129\n\t"
-        asm volatile("s_waitcnt vmcnt(11)\n\t"                                // this quad's row has arrived
-                     IG_WIDE_MAC("%0", "%4", "%5") IG_WIDE_MAC("%1", "%6", "%7") IG_WIDE_MAC("%2", "%8", "%9") IG_WIDE_MAC("%3", "%10", "%11")
-                     "s_mov_b32 m0, 0"
-                     :: "s"(mw[0]), "s"(mw[1]), "s"(mw[2]), "s"(mw[3]),
-                        "s"(wr[0]), "s"(wi[0]), "s"(wr[1]), "s"(wi[1]), "s"(wr[2]), "s"(wi[2]), "s"(wr[3]), "s"(wi[3]),
-                        "i"(80 + 2 * KQ), "i"(81 + 2 * KQ) : "memory");
-#undef IG_WIDE_MAC
-    };
-    int32_t base = 0;
-    for (int t = 0; t * TRIP < nent; ++t, base += TRIP) {
-        body(std::integral_constant<int, 0>{}, base);      body(std::integral_constant<int, 1>{}, base + 4);
-        body(std::integral_constant<int, 2>{}, base + 8);  body(std::integral_constant<int, 3>{}, base + 12);
-        body(std::integral_constant<int, 4>{}, base + 16); body(std::integral_constant<int, 5>{}, base + 20);
-        body(std::integral_constant<int, 6>{}, base + 24); body(std::integral_constant<int, 7>{}, base + 28);
-        body(std::integral_constant<int, 8>{}, base + 32); body(std::integral_constant<int, 9>{}, base + 36);
-        body(std::integral_constant<int, 10>{}, base + 40); body(std::integral_constant<int, 11>{}, base + 44);
-        // (at most 11 loads are outstanding here, all of them panel rows requested after slot B's trip was)
-        asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
-        tc = tn;
-        tn = cook_a();
-        asm volatile("v_mov_b32 v72, v76\n\tv_mov_b32 v73, v77\n\tv_mov_b32 v74, v78\n\tv_mov_b32 v75, v79" ::: "memory");
-        load_raw(std::integral_constant<int, 1>{}, t + 4);
-    }
-    flush();
-    asm volatile("s_set_gpr_idx_off");
-}
-
-// Zero the 16-row tiles of a column-major K x 64 result that no single task owns (bit clear in `owned`: tiles no nonzero
-// touches, which beta == 0 defines as zero, and the heavy tiles several tasks add into): the owning task of every other tile
-// stores all of its 16 x 64 values itself, so nothing is written twice.  A workgroup takes 4096 rows of every column.
-__global__ void __launch_bounds__(BLK)
-k_wide_zero_unowned(const uint32_t* __restrict__ owned, float2* __restrict__ Y, int64_t ldy, int64_t K) {
-    const int64_t r0 = (int64_t)blockIdx.x * 4096;
-    const int tid = threadIdx.x;
-    uint32_t own[8];          // this thread's eight 16-byte pieces q = tid + 256 u cover rows 2 q, 2 q + 1: tile q / 8
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        const int64_t tile = (r0 >> 4) + ((tid + 256 * u) >> 3);
-        own[u] = (tile << 4) < K ? ((owned[tile >> 5] >> (tile & 31)) & 1u) : 1u;
-    }
-    typedef float v4f_t __attribute__((ext_vector_type(4)));
-    const v4f_t z = {0.f, 0.f, 0.f, 0.f};
-    for (int col = 0; col < 64; ++col) {
-        v4f_t* __restrict__ dst = reinterpret_cast<v4f_t*>(Y + (int64_t)col * ldy + r0);
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-            if (!own[u]) __builtin_nontemporal_store(z, dst + tid + 256 * u);
-    }
-}
-
 // zero the flagged segments of the bricks that several tasks add into
 template <int NC>
 __global__ void __launch_bounds__(BLK)
@@ -2063,41 +1505,9 @@ int launch_gather(ig_ctx* ctx, int64_t rows, int64_t xrows, int64_t N, int64_t n
     // gathered at least about once (nnz >= xrows); always for small hot panels.
     if (!x_il && ((N >= 2 && N <= 64 && nnz >= xrows) || (xperm && N <= 64))) {
         const int np = s.CL;             // pow2 >= N, <= 64
-        const size_t need = (size_t)xrows * np * 8;
-        // The repack buffer is a per-context scratch that only grows (reported by ig_mem_info, not by the caller's own
-        // accounting): take it only while it is at most a quarter of the free device memory, otherwise -- or if the
-        // allocation fails -- run the product unpacked (slower, same result).
-        bool can_pack = need > 0 && need <= ((size_t)16 << 30);
-        if (can_pack && ctx->xpack_bytes < need) {
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
-            if (need > (free_b + ctx->xpack_bytes) / 4) can_pack = false;
-            else {
-                if (ctx->d_xpack) { IG_HIP(ctx, hipStreamSynchronize(ctx->stream)); IG_HIP(ctx, hipFree(ctx->d_xpack)); ctx->d_xpack = nullptr; ctx->xpack_bytes = 0; }
-                if (hipMalloc((void**)&ctx->d_xpack, need) != hipSuccess) { (void)hipGetLastError(); ctx->d_xpack = nullptr; can_pack = false; }
-                else ctx->xpack_bytes = need;
-            }
-        }
-        if (can_pack) {
-            ig_prof_scope prof(ctx, "pack_panel", (double)xrows * N * 8.0 + (double)need);
-            int64_t g = (xrows * np + BLK - 1) / BLK;
-            const int64_t cap = (int64_t)ctx->num_cu * 16;
-            if (g > cap) g = cap;
-            float2* xp = (float2*)ctx->d_xpack;
-            if (np == 1)      hipLaunchKernelGGL(k_pack_panel<1>, dim3((unsigned)g), dim3(BLK), 0, ctx->stream, xrows, N, X, ldx, xp, xperm);
-            else if (np == 2) hipLaunchKernelGGL(k_pack_panel<2>, dim3((unsigned)g), dim3(BLK), 0, ctx->stream, xrows, N, X, ldx, xp, xperm);
-            else if (np == 4) hipLaunchKernelGGL(k_pack_panel<4>, dim3((unsigned)g), dim3(BLK), 0, ctx->stream, xrows, N, X, ldx, xp, xperm);
-            else if (np == 8) hipLaunchKernelGGL(k_pack_panel<8>, dim3((unsigned)g), dim3(BLK), 0, ctx->stream, xrows, N, X, ldx, xp, xperm);
-            else {
-                int64_t gt = (xrows + 63) / 64;
-                if (gt > cap) gt = cap;
-                if (np == 16)      hipLaunchKernelGGL(k_pack_panel_tiled<16>, dim3((unsigned)gt), dim3(BLK), 0, ctx->stream, xrows, N, X, ldx, xp, xperm);
-                else if (np == 32) hipLaunchKernelGGL(k_pack_panel_tiled<32>, dim3((unsigned)gt), dim3(BLK), 0, ctx->stream, xrows, N, X, ldx, xp, xperm);
-                else               hipLaunchKernelGGL(k_pack_panel_tiled<64>, dim3((unsigned)gt), dim3(BLK), 0, ctx->stream, xrows, N, X, ldx, xp, xperm);
-            }
-            IG_LAUNCH_CHECK(ctx, "k_pack_panel");
-            X = xp; sxc = 1; sxr = np; packed = true;
-        }
+        const float2* xp = nullptr;      // stays null without room for the repacked panel: the product then runs unpacked
+        if (int rc = ig_pack_panel(ctx, xrows, N, np, X, ldx, xperm, true, &xp)) return rc;
+        if (xp) { X = xp; sxc = 1; sxr = np; packed = true; }
     }
     IG_REQUIRE(ctx, !xperm || packed, "csrmm: a panel-row list needs the packed path (2..64 columns and room for the repacked panel: a quarter of the free device memory, at most 16 GiB)");
     const int rpw = 64 / (s.CL * s.NL);
@@ -2161,10 +1571,9 @@ int launch_gather(ig_ctx* ctx, int64_t rows, int64_t xrows, int64_t N, int64_t n
             const int64_t tblocks = (rows + 63) / 64;
             IG_REQUIRE(ctx, tblocks <= 0x7fffffffLL, "csrmm: matrix too large for one launch");
             const int32_t tt = defer ? (thr_long < 512 ? thr_long : 512) : 0x7fffffff;
-            if (b0) hipLaunchKernelGGL((k_csrmm_rowtile64<CONJ, 0>), dim3((unsigned)tblocks), dim3(BLK), 0, ctx->stream,
-                                       rows, rowptr, colind, vals, X, Y, ldy, alpha, beta, wl, tt, thr_long);
-            else    hipLaunchKernelGGL((k_csrmm_rowtile64<CONJ, 1>), dim3((unsigned)tblocks), dim3(BLK), 0, ctx->stream,
-                                       rows, rowptr, colind, vals, X, Y, ldy, alpha, beta, wl, tt, thr_long);
+            with_flag(!b0, [&](auto bmode) {
+                hipLaunchKernelGGL((k_csrmm_rowtile64<CONJ, bmode>), dim3((unsigned)tblocks), dim3(BLK), 0, ctx->stream,
+                                   rows, rowptr, colind, vals, X, Y, ldy, alpha, beta, wl, tt, thr_long); });
         } else
         if (dense_thr > 0 && packed && b0 && bufok && nnz <= 2 * rows && N == sxr && (sxr == 8 || sxr == 4 || sxr == 2 || sxr == 1)) {
             const int32_t td = defer ? (thr_long < dense_thr ? thr_long : dense_thr) : 0x7fffffff;
@@ -2172,10 +1581,9 @@ int launch_gather(ig_ctx* ctx, int64_t rows, int64_t xrows, int64_t N, int64_t n
             // One task per wave by default: the hardware dispatcher balances the very uneven tasks better than a
             // static stride does (1.39 ms against 1.91 ms with 8 persistent workgroups per CU on the SENSE matrix).
             IG_REQUIRE(ctx, dblocks <= 0x7fffffffLL, "csrmm: matrix too large for one launch");
-#define IG_DENSE(NC_) do { if (y_il) hipLaunchKernelGGL((k_csrmm_dense64<NC_, CONJ, true>), dim3((unsigned)dblocks), dim3(BLK), 0, ctx->stream, \
-                                         rows, rowptr, colind, vals, X, Y, ldy, alpha, wl, td, thr_long, mask, dense_co);           \
-                           else hipLaunchKernelGGL((k_csrmm_dense64<NC_, CONJ, false>), dim3((unsigned)dblocks), dim3(BLK), 0, ctx->stream, \
-                                         rows, rowptr, colind, vals, X, Y, ldy, alpha, wl, td, thr_long, mask, dense_co); } while (0)
+#define IG_DENSE(NC_) with_flag(y_il, [&](auto yil) {                                                                              \
+                hipLaunchKernelGGL((k_csrmm_dense64<NC_, CONJ, yil>), dim3((unsigned)dblocks), dim3(BLK), 0, ctx->stream,           \
+                                   rows, rowptr, colind, vals, X, Y, ldy, alpha, wl, td, thr_long, mask, dense_co); })
             constexpr int dense_co = 1;
             if (sxr == 8) IG_DENSE(8); else if (sxr == 4) IG_DENSE(4); else if (sxr == 2) IG_DENSE(2);
             else hipLaunchKernelGGL((k_csrmm_dense64<1, CONJ, false>), dim3((unsigned)dblocks), dim3(BLK), 0, ctx->stream,
@@ -2201,17 +1609,15 @@ int launch_gather(ig_ctx* ctx, int64_t rows, int64_t xrows, int64_t N, int64_t n
 #define IG_GV(VW_, CLV_, NL_) do {                                                                         \
             const int rpw_v = 64 / (CLV_ * NL_);                                                           \
             const int64_t vblocks = ((rows + rpw_v - 1) / rpw_v + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;  \
-            if (b0) hipLaunchKernelGGL((k_csrmm_gather_v<VW_, CLV_, NL_, CONJ, 0>), dim3((unsigned)vblocks), dim3(BLK), 0, ctx->stream, \
-                        rows, rowptr, colind, vals, X, sxr, Y, ldy, alpha, beta, xcd, wl, thr_mid, thr_long);   \
-            else    hipLaunchKernelGGL((k_csrmm_gather_v<VW_, CLV_, NL_, CONJ, 1>), dim3((unsigned)vblocks), dim3(BLK), 0, ctx->stream, \
-                        rows, rowptr, colind, vals, X, sxr, Y, ldy, alpha, beta, xcd, wl, thr_mid, thr_long); } while (0)
+            with_flag(!b0, [&](auto bmode) {                                                               \
+                hipLaunchKernelGGL((k_csrmm_gather_v<VW_, CLV_, NL_, CONJ, bmode>), dim3((unsigned)vblocks), dim3(BLK), 0, ctx->stream, \
+                        rows, rowptr, colind, vals, X, sxr, Y, ldy, alpha, beta, xcd, wl, thr_mid, thr_long); }); } while (0)
 #define IG_GVR(VW_, CLV_, NL_) do {                                                                        \
             const int rpw_v = 64 / (CLV_ * NL_);                                                           \
             const int64_t vblocks = ((rows + rpw_v - 1) / rpw_v + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;  \
-            if (b0) hipLaunchKernelGGL((k_csrmm_gather_v<VW_, CLV_, NL_, CONJ, 0, true>), dim3((unsigned)vblocks), dim3(BLK), 0, ctx->stream, \
-                        rows, rowptr, colind, reinterpret_cast<const float2*>(rvals), X, sxr, Y, ldy, alpha, beta, xcd, wl, thr_mid, thr_long);   \
-            else    hipLaunchKernelGGL((k_csrmm_gather_v<VW_, CLV_, NL_, CONJ, 1, true>), dim3((unsigned)vblocks), dim3(BLK), 0, ctx->stream, \
-                        rows, rowptr, colind, reinterpret_cast<const float2*>(rvals), X, sxr, Y, ldy, alpha, beta, xcd, wl, thr_mid, thr_long); } while (0)
+            with_flag(!b0, [&](auto bmode) {                                                               \
+                hipLaunchKernelGGL((k_csrmm_gather_v<VW_, CLV_, NL_, CONJ, bmode, true>), dim3((unsigned)vblocks), dim3(BLK), 0, ctx->stream, \
+                        rows, rowptr, colind, reinterpret_cast<const float2*>(rvals), X, sxr, Y, ldy, alpha, beta, xcd, wl, thr_mid, thr_long); }); } while (0)
             if (rvals && N == 8 && vw >= 4 && vw < 8) IG_GVR(4, 2, 8);
             else if (rvals && N == 4) IG_GVR(2, 2, 8);
             else if (rvals && N == 2) IG_GVR(2, 1, 8);
@@ -2228,10 +1634,9 @@ int launch_gather(ig_ctx* ctx, int64_t rows, int64_t xrows, int64_t N, int64_t n
                     IG_REQUIRE(ctx, tblocks <= 0x7fffffffLL, "csrmm: matrix too large for one launch");
                     // (waves per 64-row tile, measured: 4 -> 1.77-1.85 ms, 8 -> 1.82, 16 -> 1.97: one big workgroup per CU loses the
                     // overlap between workgroups and gains nothing from the smaller L2 footprint)
-                    if (b0) hipLaunchKernelGGL((k_csrmm_gather_tile64<CONJ, 0, 4>), dim3((unsigned)tblocks), dim3(256), 0, ctx->stream,
-                                rows, nnz, rowptr, colind, vals, X, Y, ldy, alpha, beta, xcd, wl, thr_long);
-                    else    hipLaunchKernelGGL((k_csrmm_gather_tile64<CONJ, 1, 4>), dim3((unsigned)tblocks), dim3(256), 0, ctx->stream,
-                                rows, nnz, rowptr, colind, vals, X, Y, ldy, alpha, beta, xcd, wl, thr_long);
+                    with_flag(!b0, [&](auto bmode) {
+                        hipLaunchKernelGGL((k_csrmm_gather_tile64<CONJ, bmode, 4>), dim3((unsigned)tblocks), dim3(256), 0, ctx->stream,
+                                rows, nnz, rowptr, colind, vals, X, Y, ldy, alpha, beta, xcd, wl, thr_long); });
                 }
                 else IG_GV(4, 16, 4);                                                                      // 64 columns: 16 nonzeros per trip
             } else {                                          // short rows (a transposed gridding matrix): one trip each
@@ -2244,14 +1649,10 @@ int launch_gather(ig_ctx* ctx, int64_t rows, int64_t xrows, int64_t N, int64_t n
             IG_LAUNCH_CHECK(ctx, "k_csrmm_gather_v");
         } else {
 #define IG_GATHER(CL_, NL_)                                                                        \
-    do {                                                                                           \
-        if (b0) hipLaunchKernelGGL((k_csrmm_gather<CL_, NL_, CONJ, 0>), dim3((unsigned)blocks),    \
+    with_flag(!b0, [&](auto bmode) {                                                               \
+        hipLaunchKernelGGL((k_csrmm_gather<CL_, NL_, CONJ, bmode>), dim3((unsigned)blocks),        \
                     dim3(BLK), 0, ctx->stream, rows, N, rowptr, colind, vals, X, sxc, sxr, Y, ldy, \
-                    alpha, beta, xcd, wl, thr_mid, thr_long);                                      \
-        else    hipLaunchKernelGGL((k_csrmm_gather<CL_, NL_, CONJ, 1>), dim3((unsigned)blocks),    \
-                    dim3(BLK), 0, ctx->stream, rows, N, rowptr, colind, vals, X, sxc, sxr, Y, ldy, \
-                    alpha, beta, xcd, wl, thr_mid, thr_long);                                      \
-    } while (0)
+                    alpha, beta, xcd, wl, thr_mid, thr_long); })
 #define IG_NL_SWITCH(CL_, MACRO)                                                                   \
     switch (s.NL) {                                                                                \
         case 1:  MACRO(CL_, 1); break;                                                             \
@@ -2283,17 +1684,15 @@ int launch_gather(ig_ctx* ctx, int64_t rows, int64_t xrows, int64_t N, int64_t n
     do {                                                                                           \
         if (thr_mid < thr_long || rowlane) {                                                       \
             ig_prof_scope prof(ctx, "csrmm_rows_wave");                                            \
-            if (b0) hipLaunchKernelGGL((k_csrmm_rows_wave<CL_, CONJ, 0>), dim3(gw), dim3(BLK), 0, ctx->stream, \
-                        N, rowptr, colind, vals, X, sxc, sxr, Y, ldy, syr, alpha, beta, wl.rows[0], wl.count, wl.cap, wl.yperm);   \
-            else    hipLaunchKernelGGL((k_csrmm_rows_wave<CL_, CONJ, 1>), dim3(gw), dim3(BLK), 0, ctx->stream, \
-                        N, rowptr, colind, vals, X, sxc, sxr, Y, ldy, syr, alpha, beta, wl.rows[0], wl.count, wl.cap, wl.yperm);   \
+            with_flag(!b0, [&](auto bmode) {                                                       \
+                hipLaunchKernelGGL((k_csrmm_rows_wave<CL_, CONJ, bmode>), dim3(gw), dim3(BLK), 0, ctx->stream, \
+                        N, rowptr, colind, vals, X, sxc, sxr, Y, ldy, syr, alpha, beta, wl.rows[0], wl.count, wl.cap, wl.yperm); }); \
         }                                                                                          \
         {                                                                                          \
             ig_prof_scope prof(ctx, "csrmm_rows_block");                                           \
-            if (b0) hipLaunchKernelGGL((k_csrmm_rows_block<CL_, CONJ, 0>), dim3(gb), dim3(1024), 0, ctx->stream, \
-                        N, rowptr, colind, vals, X, sxc, sxr, Y, ldy, syr, alpha, beta, wl.rows[1], wl.count + WL_SUB, wl.cap, wl.yperm); \
-            else    hipLaunchKernelGGL((k_csrmm_rows_block<CL_, CONJ, 1>), dim3(gb), dim3(1024), 0, ctx->stream, \
-                        N, rowptr, colind, vals, X, sxc, sxr, Y, ldy, syr, alpha, beta, wl.rows[1], wl.count + WL_SUB, wl.cap, wl.yperm); \
+            with_flag(!b0, [&](auto bmode) {                                                       \
+                hipLaunchKernelGGL((k_csrmm_rows_block<CL_, CONJ, bmode>), dim3(gb), dim3(1024), 0, ctx->stream, \
+                        N, rowptr, colind, vals, X, sxc, sxr, Y, ldy, syr, alpha, beta, wl.rows[1], wl.count + WL_SUB, wl.cap, wl.yperm); }); \
         }                                                                                          \
     } while (0)
         switch (s.CL) {
@@ -2320,8 +1719,7 @@ int launch_panel_scale(ig_ctx* ctx, int64_t rows, int64_t N, float2* Y, int64_t 
         IG_HIP(ctx, hipMemsetAsync(Y, 0, (size_t)rows * (size_t)N * 8, ctx->stream));
         return IG_OK;
     }
-    if (zero) hipLaunchKernelGGL(k_panel_scale<true>,  dim3((unsigned)gx, (unsigned)N), dim3(BLK), 0, ctx->stream, rows, N, Y, ld, beta);
-    else      hipLaunchKernelGGL(k_panel_scale<false>, dim3((unsigned)gx, (unsigned)N), dim3(BLK), 0, ctx->stream, rows, N, Y, ld, beta);
+    with_flag(zero, [&](auto z) { hipLaunchKernelGGL(k_panel_scale<z>, dim3((unsigned)gx, (unsigned)N), dim3(BLK), 0, ctx->stream, rows, N, Y, ld, beta); });
     IG_LAUNCH_CHECK(ctx, "k_panel_scale");
     return IG_OK;
 }
@@ -2358,6 +1756,17 @@ int check_panel_args(ig_ctx* ctx, const char* who, int64_t xrows, int64_t yrows,
     IG_REQUIRE(ctx, N == 0 || xrows == 0 || X != nullptr, "%s: X is NULL", who);
     IG_REQUIRE(ctx, N <= 1 || ldx >= xrows, "%s: ldx (%lld) smaller than X rows (%lld)", who, (long long)ldx, (long long)xrows);
     IG_REQUIRE(ctx, N <= 1 || ldy >= yrows, "%s: ldy (%lld) smaller than Y rows (%lld)", who, (long long)ldy, (long long)yrows);
+    return IG_OK;
+}
+
+// The K result rows as a grid of n0 x nm x ... points: *mask = the third part of the support table, one bit per 16-row segment
+// (after the z ranges and the y ranges).  No table: every row.
+int grid_mask(ig_ctx* ctx, const char* who, int64_t K, const int16_t* support, int64_t n0, int64_t nm, GridMask* mask) {
+    IG_REQUIRE(ctx, !support || (n0 > 0 && nm > 0 && n0 % 16 == 0 && nm % 16 == 0 && nm <= 512 && K % (n0 * nm) == 0 && K < 0x7fffffffLL),
+               "%s: rows (%lld) are not a grid of n0=%lld (multiple of 16) x nm=%lld (multiple of 16, <= 512) x ...",
+               who, (long long)K, (long long)n0, (long long)nm);
+    const int64_t ns = support ? K / (n0 * nm) : 0, nt = n0 / 16;
+    *mask = GridMask{support ? reinterpret_cast<const uint32_t*>(support + 2 * (ns * nt + nt)) : nullptr, n0, nm};
     return IG_OK;
 }
 
@@ -2434,20 +1843,14 @@ int ig_ccsrmm_t_grid(ig_ctx* ctx, int64_t M, int64_t K, int64_t N, int64_t nnz,
                      const int16_t* support, int64_t n0, int64_t nm, const int32_t* xrow_perm) {
     IG_REQUIRE(ctx, ctx != nullptr, "ig_ccsrmm_t_grid: ctx is NULL");
     if (int rc = check_panel_args(ctx, "ig_ccsrmm_t_grid", M, K, N, nnz, vals_t, colind_t, rowptr_t, X, ldx, Y, ldy)) return rc;
-    IG_REQUIRE(ctx, !support || (n0 > 0 && nm > 0 && n0 % 16 == 0 && nm % 16 == 0 && nm <= 512 && K % (n0 * nm) == 0 && K < 0x7fffffffLL),
-               "ig_ccsrmm_t_grid: rows (%lld) are not a grid of n0=%lld (multiple of 16) x nm=%lld (multiple of 16, <= 512) x ...",
-               (long long)K, (long long)n0, (long long)nm);
+    GridMask mask;
+    if (int rc = grid_mask(ctx, "ig_ccsrmm_t_grid", K, support, n0, nm, &mask)) return rc;
     if (N == 0 || K == 0) return IG_OK;
     if (int rc = ig_set_device(ctx)) return rc;
-    // third part of the support table: one bit per 16-row segment (after the z ranges and the y ranges)
-    const int64_t ns = support ? K / (n0 * nm) : 0, nt = n0 / 16;
-    GridMask mask{support ? reinterpret_cast<const uint32_t*>(support + 2 * (ns * nt + nt)) : nullptr, n0, nm};
     return launch_gather<true>(ctx, K, M, N, nnz, rowptr_t, colind_t, (const float2*)vals_t,
                                (const float2*)X, ldx, (float2*)Y, ldy,
                                make_float2(ar, ai), make_float2(br, bi), mask, nullptr, xrow_perm);
 }
-
-// ---- host-side structure analysis -------------------------------------------
 
 int ig_ccsrmm_il(ig_ctx* ctx, int64_t M, int64_t K, int64_t N, int64_t nnz,
                  float ar, float ai, const void* vals, const int32_t* colind, const int32_t* rowptr,
@@ -2485,24 +1888,16 @@ int ig_ccsrmm_t_grid_il(ig_ctx* ctx, int64_t M, int64_t K, int64_t N, int64_t nn
     IG_REQUIRE(ctx, ctx != nullptr, "ig_ccsrmm_t_grid_il: ctx is NULL");
     if (int rc = check_panel_args(ctx, "ig_ccsrmm_t_grid_il", M, K, N, nnz, vals_t, colind_t, rowptr_t, X, ldx, Y_il, K)) return rc;
     IG_REQUIRE(ctx, N == 2 || N == 4 || N == 8, "ig_ccsrmm_t_grid_il: 2, 4 or 8 columns (got %lld)", (long long)N);
-    IG_REQUIRE(ctx, !support || (n0 > 0 && nm > 0 && n0 % 16 == 0 && nm % 16 == 0 && nm <= 512 && K % (n0 * nm) == 0 && K < 0x7fffffffLL),
-               "ig_ccsrmm_t_grid_il: rows (%lld) are not a grid of n0=%lld (multiple of 16) x nm=%lld (multiple of 16, <= 512) x ...",
-               (long long)K, (long long)n0, (long long)nm);
+    GridMask mask;
+    if (int rc = grid_mask(ctx, "ig_ccsrmm_t_grid_il", K, support, n0, nm, &mask)) return rc;
     if (K == 0) return IG_OK;
     if (int rc = ig_set_device(ctx)) return rc;
-    const int64_t ns = support ? K / (n0 * nm) : 0, nt = n0 / 16;
-    GridMask mask{support ? reinterpret_cast<const uint32_t*>(support + 2 * (ns * nt + nt)) : nullptr, n0, nm};
     return launch_gather<true>(ctx, K, M, N, nnz, rowptr_t, colind_t, (const float2*)vals_t,
                                (const float2*)X, ldx, (float2*)Y_il, K, make_float2(ar, ai), make_float2(0.f, 0.f),
                                mask, nullptr, nullptr, false, true);
 }
 
 namespace {
-inline bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
-inline bool bricks_ok(int64_t n0, int64_t nm, int64_t ns, int bm, int bs, int unit) {
-    return n0 > 0 && nm > 0 && ns > 0 && pow2(bm) && pow2(bs) && bm * bs <= 64 && n0 % 16 == 0 && nm % bm == 0 && ns % bs == 0 &&
-           pow2(unit) && unit <= 64;
-}
 // the bricks one row touches and how many of its nonzeros fall into each (a row touches few bricks: linear search)
 struct RowBricks {
     int64_t id[64]; int32_t cnt[64]; int n = 0;
@@ -2520,13 +1915,6 @@ struct RowBricks {
 // per-thread counts into per-thread cursors.  (Single-threaded this was 4 s of the headline problem's 8 s of setup.)
 namespace {
 struct BrickGeom { int64_t n0, nm, ns, nbx, nbm, nbs, nb; int bm, bs, unit; };
-inline int brick_threads(int64_t M) {
-    unsigned hw = std::thread::hardware_concurrency();
-    int nt = (int)(hw ? hw : 4);
-    if (nt > 16) nt = 16;
-    if (M < 16384) nt = 1;
-    return nt;
-}
 // per-brick padded entry counts of rows [lo, hi); returns 0, or 1 (column outside the grid), 2 (a row touches > 64 bricks)
 int count_rows(const BrickGeom& g, const int32_t* rowptr, const int32_t* colind, int64_t lo, int64_t hi, int32_t* cnt, int* overflow) {
     const int64_t P = g.n0 * g.nm * g.ns;
@@ -2545,12 +1933,6 @@ int count_rows(const BrickGeom& g, const int32_t* rowptr, const int32_t* colind,
         }
     }
     return 0;
-}
-void run_threads(int nt, const std::function<void(int)>& body) {
-    if (nt == 1) { body(0); return; }
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t) th.emplace_back([t, &body]() { body(t); });
-    for (auto& x : th) x.join();
 }
 }  // namespace
 
@@ -2682,22 +2064,8 @@ int ig_ccsrmm_t_bricks(ig_ctx* ctx, int64_t M, int64_t K, int64_t N, float ar, f
     const uint32_t* bits = support ? reinterpret_cast<const uint32_t*>(support + 2 * (ns * snt + snt)) : nullptr;
     const float2 alpha = make_float2(ar, ai);
     // the k-space panel as packed rows [t][N] (column-major in, as everywhere at the boundary)
-    const size_t need = (size_t)M * N * 8;
-    if (ctx->xpack_bytes < need) {
-        if (ctx->d_xpack) { IG_HIP(ctx, hipStreamSynchronize(ctx->stream)); IG_HIP(ctx, hipFree(ctx->d_xpack)); ctx->d_xpack = nullptr; ctx->xpack_bytes = 0; }
-        IG_HIP(ctx, hipMalloc((void**)&ctx->d_xpack, need));
-        ctx->xpack_bytes = need;
-    }
-    float2* xp = (float2*)ctx->d_xpack;
-    {
-        ig_prof_scope prof(ctx, "pack_panel", 2.0 * (double)need);
-        int64_t g = (M * N + BLK - 1) / BLK;
-        const int64_t cap = (int64_t)ctx->num_cu * 16;
-        if (g > cap) g = cap;
-        if (N == 4) hipLaunchKernelGGL(k_pack_panel<4>, dim3((unsigned)g), dim3(BLK), 0, ctx->stream, M, N, (const float2*)X, ldx, xp, (const int32_t*)nullptr);
-        else        hipLaunchKernelGGL(k_pack_panel<8>, dim3((unsigned)g), dim3(BLK), 0, ctx->stream, M, N, (const float2*)X, ldx, xp, (const int32_t*)nullptr);
-        IG_LAUNCH_CHECK(ctx, "k_pack_panel");
-    }
+    const float2* xp = nullptr;
+    if (int rc = ig_pack_panel(ctx, M, N, (int)N, (const float2*)X, ldx, nullptr, false, &xp)) return rc;
     int bm_log2 = 0, bs_log2 = 0;
     while ((1 << bm_log2) < bm) ++bm_log2;
     while ((1 << bs_log2) < bs) ++bs_log2;
@@ -2711,10 +2079,9 @@ int ig_ccsrmm_t_bricks(ig_ctx* ctx, int64_t M, int64_t K, int64_t N, float ar, f
             ig_prof_scope prof(ctx, "grid_bricks_zero");                                                                        \
             hipLaunchKernelGGL((k_grid_bricks_zero<NC_>), dim3((unsigned)nshared), dim3(BLK), 0, ctx->stream, shared_bricks, (float2*)Y_il, bits, (int)n0, (int)nm, bm_log2, bs_log2, nbx, nbm, st_log2, zw); } \
         ig_prof_scope prof(ctx, "csrmm_bricks_conj");                                                                           \
-        if (realw) hipLaunchKernelGGL((k_grid_bricks<NC_, NSEG_, PAIR_, true>), dim3(blocks), dim3(BLK), lds, ctx->stream, (const BrickTask*)tasks, (int)ntasks, (const BrickRef*)brick_table, (const BrickEntry*)entries, round_rows, \
-                           (const float2*)xp, (float2*)Y_il, alpha, bits, (int)n0, (int)nm, bm_log2, bs_log2, nbx, nbm, st_log2, zw); \
-        else hipLaunchKernelGGL((k_grid_bricks<NC_, NSEG_, PAIR_, false>), dim3(blocks), dim3(BLK), lds, ctx->stream, (const BrickTask*)tasks, (int)ntasks, (const BrickRef*)brick_table, (const BrickEntry*)entries, round_rows, \
-                           (const float2*)xp, (float2*)Y_il, alpha, bits, (int)n0, (int)nm, bm_log2, bs_log2, nbx, nbm, st_log2, zw); } while (0)
+        with_flag(realw, [&](auto rw) {                                                                                         \
+            hipLaunchKernelGGL((k_grid_bricks<NC_, NSEG_, PAIR_, rw>), dim3(blocks), dim3(BLK), lds, ctx->stream, (const BrickTask*)tasks, (int)ntasks, (const BrickRef*)brick_table, (const BrickEntry*)entries, round_rows, \
+                           xp, (float2*)Y_il, alpha, bits, (int)n0, (int)nm, bm_log2, bs_log2, nbx, nbm, st_log2, zw); }); } while (0)
     const int nseg_total = (16 / support_tile) * bm * bs;
     if (N == 8 && nseg_total == 4) IG_BRICKS(8, 4);
     else if (N == 8 && nseg_total == 8) IG_BRICKS(8, 8);
@@ -2829,22 +2196,8 @@ int ig_ccsrmm_t_slots(ig_ctx* ctx, int64_t M, int64_t K, int64_t N, float ar, fl
     const float2 alpha = make_float2(ar, ai);
     // the k-space panel as packed rows [t][N] (one column: it already is)
     const float2* xp = (const float2*)X;
-    if (N > 1) {
-        const size_t need = (size_t)M * N * 8;
-        if (ctx->xpack_bytes < need) {
-            if (ctx->d_xpack) { IG_HIP(ctx, hipStreamSynchronize(ctx->stream)); IG_HIP(ctx, hipFree(ctx->d_xpack)); ctx->d_xpack = nullptr; ctx->xpack_bytes = 0; }
-            IG_HIP(ctx, hipMalloc((void**)&ctx->d_xpack, need));
-            ctx->xpack_bytes = need;
-        }
-        ig_prof_scope prof(ctx, "pack_panel", 2.0 * (double)need);
-        int64_t g = (M * N + BLK - 1) / BLK;
-        const int64_t cap = (int64_t)ctx->num_cu * 16;
-        if (g > cap) g = cap;
-        if (N == 2) hipLaunchKernelGGL(k_pack_panel<2>, dim3((unsigned)g), dim3(BLK), 0, ctx->stream, M, N, (const float2*)X, ldx, (float2*)ctx->d_xpack, (const int32_t*)nullptr);
-        else        hipLaunchKernelGGL(k_pack_panel<4>, dim3((unsigned)g), dim3(BLK), 0, ctx->stream, M, N, (const float2*)X, ldx, (float2*)ctx->d_xpack, (const int32_t*)nullptr);
-        IG_LAUNCH_CHECK(ctx, "k_pack_panel");
-        xp = (const float2*)ctx->d_xpack;
-    }
+    if (N > 1)
+        if (int rc = ig_pack_panel(ctx, M, N, (int)N, (const float2*)X, ldx, nullptr, false, &xp)) return rc;
     int bm_log2 = 0, bs_log2 = 0;
     while ((1 << bm_log2) < bm) ++bm_log2;
     while ((1 << bs_log2) < bs) ++bs_log2;
@@ -2857,184 +2210,16 @@ int ig_ccsrmm_t_slots(ig_ctx* ctx, int64_t M, int64_t K, int64_t N, float ar, fl
             ig_prof_scope prof(ctx, "grid_bricks_zero");                                                                        \
             hipLaunchKernelGGL((k_grid_bricks_zero<NC_>), dim3((unsigned)nshared), dim3(BLK), 0, ctx->stream, shared_bricks, (float2*)Y_il, bits, (int)n0, (int)nm, bm_log2, bs_log2, nbx, nbm, st_log2, zw); } \
         ig_prof_scope prof(ctx, "csrmm_slots_conj");                                                                            \
-        if (realw) hipLaunchKernelGGL((k_grid_slots<NC_, true>), dim3(blocks), dim3(BLK), lds, ctx->stream, (const BrickTask*)tasks, (int)ntasks, (const BrickRef*)brick_table, slot_ptr, (const SlotEntry*)entries16, \
-                           xp, (float2*)Y_il, alpha, bits, (int)n0, (int)nm, bm_log2, bs_log2, nbx, nbm, st_log2, zw); \
-        else hipLaunchKernelGGL((k_grid_slots<NC_, false>), dim3(blocks), dim3(BLK), lds, ctx->stream, (const BrickTask*)tasks, (int)ntasks, (const BrickRef*)brick_table, slot_ptr, (const SlotEntry*)entries16, \
-                           xp, (float2*)Y_il, alpha, bits, (int)n0, (int)nm, bm_log2, bs_log2, nbx, nbm, st_log2, zw); } while (0)
+        with_flag(realw, [&](auto rw) {                                                                                         \
+            hipLaunchKernelGGL((k_grid_slots<NC_, rw>), dim3(blocks), dim3(BLK), lds, ctx->stream, (const BrickTask*)tasks, (int)ntasks, (const BrickRef*)brick_table, slot_ptr, (const SlotEntry*)entries16, \
+                           xp, (float2*)Y_il, alpha, bits, (int)n0, (int)nm, bm_log2, bs_log2, nbx, nbm, st_log2, zw); }); } while (0)
     if (N == 1) IG_SLOTS(1); else if (N == 2) IG_SLOTS(2); else IG_SLOTS(4);
 #undef IG_SLOTS
     IG_LAUNCH_CHECK(ctx, "k_grid_slots");
     return IG_OK;
 }
 
-int ig_ccsrmm_t_bricks_wide(ig_ctx* ctx, int64_t M, int64_t K, float ar, float ai,
-                            const void* entries, const uint32_t* entry_rows, const void* X, int64_t ldx, void* Y, int64_t ldy,
-                            const int32_t* tasks, int64_t ntasks, const int32_t* brick_table, const uint32_t* owned_tiles) {
-    return ig_ccsrmm_t_bricks_wide_grid(ctx, M, K, ar, ai, entries, entry_rows, X, ldx, Y, ldy, tasks, ntasks, brick_table, owned_tiles, 0, 0, 1, 1, 3);
-}
-
-int ig_ccsrmm_t_bricks_wide_grid(ig_ctx* ctx, int64_t M, int64_t K, float ar, float ai,
-                                 const void* entries, const uint32_t* entry_rows, const void* X, int64_t ldx, void* Y, int64_t ldy,
-                                 const int32_t* tasks, int64_t ntasks, const int32_t* brick_table, const uint32_t* owned_tiles,
-                                 int64_t n0, int64_t nm, int bm, int bs, int entry_words) {
-    IG_REQUIRE(ctx, ctx != nullptr, "ig_ccsrmm_t_bricks_wide: ctx is NULL");
-    const int64_t N = 64;
-    const bool grid = bm * bs > 1;
-    IG_REQUIRE(ctx, entry_words == 3 || (entry_words == 2 && grid), "ig_ccsrmm_t_bricks_wide_grid: entries of 3 words {cell, re, im}, or 2 {cell, re} (grid bricks only); got %d", entry_words);
-    IG_REQUIRE(ctx, !grid || (n0 > 0 && nm > 0 && K % (n0 * nm) == 0 && bricks_ok(n0, nm, K / (n0 * nm), bm, bs, 1) && bm * bs <= 4),
-               "ig_ccsrmm_t_bricks_wide_grid: rows (%lld) are not a grid of n0=%lld x nm=%lld x ... that divides into 16 x %d x %d bricks (bm * bs <= 4)",
-               (long long)K, (long long)n0, (long long)nm, bm, bs);
-    IG_REQUIRE(ctx, M >= 0 && K >= 0 && K % 16 == 0 && K <= 0x7fffffffLL, "ig_ccsrmm_t_bricks_wide: K (%lld) must be a multiple of 16", (long long)K);
-    IG_REQUIRE(ctx, (ntasks == 0 || (entries && entry_rows && tasks && brick_table)) && (M == 0 || X) && (K == 0 || Y) && ldx >= M && ldy >= K,
-               "ig_ccsrmm_t_bricks_wide: NULL array or short leading dimension");
-    IG_REQUIRE(ctx, ntasks >= 0 && ntasks <= 0x7fffffffLL, "ig_ccsrmm_t_bricks_wide: bad task list");
-    IG_REQUIRE(ctx, M * N * 8 < 0x7fffffffLL, "ig_ccsrmm_t_bricks_wide: the panel (%lld x 64) exceeds the 2 GB window of a buffer descriptor", (long long)M);
-    if (K == 0) return IG_OK;
-    if (int rc = ig_set_device(ctx)) return rc;
-    if (owned_tiles && ntasks > 0 && M > 0 && (reinterpret_cast<uintptr_t>(Y) & 15u) == 0 && ldy % 2 == 0) {
-        // every tile is written exactly once: here if no task owns it, by its owner's flush otherwise
-        ig_prof_scope prof(ctx, "bricks_wide_zero");
-        hipLaunchKernelGGL(k_wide_zero_unowned, dim3((unsigned)((K + 4095) / 4096)), dim3(BLK), 0, ctx->stream, owned_tiles, (float2*)Y, ldy, K);
-        IG_LAUNCH_CHECK(ctx, "k_wide_zero_unowned");
-    } else {
-        ig_prof_scope prof(ctx, "bricks_wide_zero", (double)K * N * 8.0);
-        if (ldy == K) IG_HIP(ctx, hipMemsetAsync(Y, 0, (size_t)K * N * 8, ctx->stream));
-        else IG_HIP(ctx, hipMemset2DAsync(Y, (size_t)ldy * 8, 0, (size_t)K * 8, (size_t)N, ctx->stream));
-    }
-    if (ntasks == 0 || M == 0) return IG_OK;
-    const size_t need = (size_t)M * N * 8;
-    if (ctx->xpack_bytes < need) {
-        if (ctx->d_xpack) { IG_HIP(ctx, hipStreamSynchronize(ctx->stream)); IG_HIP(ctx, hipFree(ctx->d_xpack)); ctx->d_xpack = nullptr; ctx->xpack_bytes = 0; }
-        IG_HIP(ctx, hipMalloc((void**)&ctx->d_xpack, need));
-        ctx->xpack_bytes = need;
-    }
-    float2* xp = (float2*)ctx->d_xpack;
-    {
-        ig_prof_scope prof(ctx, "pack_panel", 2.0 * (double)need);
-        int64_t gt = (M + 63) / 64;
-        const int64_t cap = (int64_t)ctx->num_cu * 16;
-        if (gt > cap) gt = cap;
-        hipLaunchKernelGGL(k_pack_panel_tiled<64>, dim3((unsigned)gt), dim3(BLK), 0, ctx->stream, M, N, (const float2*)X, ldx, xp, (const int32_t*)nullptr);
-        IG_LAUNCH_CHECK(ctx, "k_pack_panel");
-    }
-    ig_prof_scope prof(ctx, "csrmm_bricks_wide_conj");
-    const unsigned blocks = (unsigned)((ntasks + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-    if (grid) {
-        int bm_log2 = 0, bs_log2 = 0;
-        while ((1 << bm_log2) < bm) ++bm_log2;
-        while ((1 << bs_log2) < bs) ++bs_log2;
-        const int nbx = (int)(n0 / 16), nbm = (int)(nm / bm);
-#define IG_WIDE_R(NT_) do { if (entry_words == 2) hipLaunchKernelGGL((k_bricks_wide64r<NT_, true>), dim3(blocks), dim3(BLK), 0, ctx->stream, (const BrickTask*)tasks, (int)ntasks, (const BrickRef*)brick_table, \
-                       (const BrickEntry*)entries, entry_rows, (const float2*)xp, (float2*)Y, ldy, make_float2(ar, ai), (int)n0, (int)nm, bm_log2, bs_log2, nbx, nbm); \
-                       else hipLaunchKernelGGL((k_bricks_wide64r<NT_, false>), dim3(blocks), dim3(BLK), 0, ctx->stream, (const BrickTask*)tasks, (int)ntasks, (const BrickRef*)brick_table, \
-                       (const BrickEntry*)entries, entry_rows, (const float2*)xp, (float2*)Y, ldy, make_float2(ar, ai), (int)n0, (int)nm, bm_log2, bs_log2, nbx, nbm); } while (0)
-        if (bm * bs == 2) IG_WIDE_R(2); else IG_WIDE_R(4);
-#undef IG_WIDE_R
-        IG_LAUNCH_CHECK(ctx, "k_bricks_wide64r");
-        return IG_OK;
-    }
-    hipLaunchKernelGGL(k_bricks_wide64, dim3(blocks), dim3(BLK), 0, ctx->stream, (const BrickTask*)tasks, (int)ntasks, (const BrickRef*)brick_table,
-                       (const BrickEntry*)entries, entry_rows, (const float2*)xp, (float2*)Y, ldy, make_float2(ar, ai));
-    IG_LAUNCH_CHECK(ctx, "k_bricks_wide64");
-    return IG_OK;
-}
-
-// The run format of k_csrmm_runs64r from a CSR with sorted rows: the nonzeros of every run of 16 consecutive rows grouped by
-// column.  Two calls: dcols == NULL counts (run_dptr[nruns + 1] = prefix sums of the runs' distinct columns), the second fills
-// dcols (run_dptr[nruns] words) and entries (nnz x 12 bytes).  *all_real = every value has a zero imaginary part.
-// IG_ERR_UNSUPPORTED when a row holds a column twice or a column index needs more than 27 bits.
-int ig_csr_runs_build(int64_t M, int64_t K, const int32_t* rowptr, const int32_t* colind, const void* vals,
-                      int32_t* run_dptr, uint32_t* dcols, void* entries, int* all_real) {
-    if (M < 0 || !rowptr || !run_dptr || (rowptr[M] > rowptr[0] && (!colind || !vals)) || (dcols && !entries))
-        return ig_fail(nullptr, IG_ERR_ARG, "ig_csr_runs_build: bad arguments");
-    if (K > (1LL << 27)) return ig_fail(nullptr, IG_ERR_UNSUPPORTED, "ig_csr_runs_build: column indices need more than 27 bits");
-    const int64_t nruns = (M + RUN_ROWS - 1) / RUN_ROWS;
-    const float2* v = (const float2*)vals;
-    RunEntry* out = (RunEntry*)entries;
-    const int nt = brick_threads(M);
-    const int64_t per = (nruns + nt - 1) / nt;
-    std::atomic<int> bad{0}, cplx{0};
-    if (!dcols) run_dptr[0] = 0;
-    run_threads(nt, [&](int th) {
-        struct Nz { int32_t col; uint32_t row; float2 val; };
-        std::vector<Nz> buf;
-        const int64_t lo = std::min<int64_t>(nruns, th * per), hi = std::min<int64_t>(nruns, lo + per);
-        for (int64_t r = lo; r < hi; ++r) {
-            const int64_t rlo = r * RUN_ROWS, rhi = std::min<int64_t>(M, rlo + RUN_ROWS);
-            buf.clear();
-            for (int64_t t = rlo; t < rhi; ++t)
-                for (int32_t p = rowptr[t]; p < rowptr[t + 1]; ++p) {
-                    if (colind[p] < 0 || colind[p] >= K) { bad = 1; continue; }
-                    buf.push_back(Nz{colind[p], (uint32_t)(t - rlo), v[p]});
-                }
-            std::stable_sort(buf.begin(), buf.end(), [](const Nz& a, const Nz& b) { return a.col < b.col; });
-            int32_t nd = 0;
-            for (size_t i = 0; i < buf.size(); ++i) {
-                if (i == 0 || buf[i].col != buf[i - 1].col) ++nd;
-                else if (buf[i].row == buf[i - 1].row) bad = 1;                       // a row holds a column twice
-            }
-            if (!dcols) { run_dptr[r + 1] = nd; continue; }                           // counting pass: sizes, prefix-summed below
-            uint32_t* dc = dcols + run_dptr[r];
-            RunEntry* e = out + (rowptr[rlo] - rowptr[0]);
-            int32_t j = -1;
-            for (size_t i = 0; i < buf.size(); ++i) {
-                if (i == 0 || buf[i].col != buf[i - 1].col) { ++j; dc[j] = (uint32_t)buf[i].col; }
-                else dc[j] += 1u << 27;
-                e[i] = RunEntry{buf[i].row, buf[i].val.x, buf[i].val.y};
-                if (buf[i].val.y != 0.f) cplx = 1;
-            }
-        }
-    });
-    if (bad) return ig_fail(nullptr, IG_ERR_UNSUPPORTED, "ig_csr_runs_build: a column index outside the matrix, or a row that holds a column twice");
-    if (!dcols) {
-        for (int64_t r = 0; r < nruns; ++r) {
-            const int64_t sum = (int64_t)run_dptr[r] + run_dptr[r + 1];
-            if (sum > 0x7fffffffLL) return ig_fail(nullptr, IG_ERR_UNSUPPORTED, "ig_csr_runs_build: more than 2^31 distinct columns");
-            run_dptr[r + 1] = (int32_t)sum;
-        }
-    } else if (all_real) *all_real = cplx ? 0 : 1;
-    return IG_OK;
-}
-
-// Y = beta*Y + alpha * A' * X[xrows, :] like ig_ccsrmm_xrows, for 64 columns, through the run format of A' (ig_csr_runs_build on the
-// compact column indices): the panel's touched rows are repacked row-major, then k_csrmm_runs64r.
-int ig_ccsrmm_xrows_runs(ig_ctx* ctx, int64_t M, int64_t K, int64_t nnz, float ar, float ai, const int32_t* rowptr,
-                         const int32_t* run_dptr, const uint32_t* dcols, const void* entries, int all_real, const int32_t* run_order,
-                         const void* X, int64_t ldx, float br, float bi, void* Y, int64_t ldy, const int32_t* xrows, int64_t nxrows) {
-    IG_REQUIRE(ctx, ctx != nullptr, "ig_ccsrmm_xrows_runs: ctx is NULL");
-    IG_REQUIRE(ctx, M >= 0 && K >= 0 && nnz >= 0 && nnz <= 0x7fffffffLL && M <= 0x7fffffffLL, "ig_ccsrmm_xrows_runs: bad dimensions");
-    IG_REQUIRE(ctx, rowptr && run_dptr && (nnz == 0 || (dcols && entries)) && (M == 0 || Y) && ldy >= M && ldx >= K, "ig_ccsrmm_xrows_runs: NULL array or short leading dimension");
-    IG_REQUIRE(ctx, nxrows >= 1 && nxrows <= K && xrows && X && nxrows * 512 < 0xffffffffLL, "ig_ccsrmm_xrows_runs: bad row list (1 .. 2^23 - 1 rows: the repacked panel is addressed with 32 bits)");
-    IG_REQUIRE(ctx, nnz * 12 < 0x7fffffffLL, "ig_ccsrmm_xrows_runs: the entries exceed the 2 GB window of a buffer descriptor");
-    if (M == 0) return IG_OK;
-    if (int rc = ig_set_device(ctx)) return rc;
-    const size_t need = (size_t)nxrows * 512;
-    if (ctx->xpack_bytes < need) {
-        if (ctx->d_xpack) { IG_HIP(ctx, hipStreamSynchronize(ctx->stream)); IG_HIP(ctx, hipFree(ctx->d_xpack)); ctx->d_xpack = nullptr; ctx->xpack_bytes = 0; }
-        IG_HIP(ctx, hipMalloc((void**)&ctx->d_xpack, need));
-        ctx->xpack_bytes = need;
-    }
-    float2* xp = (float2*)ctx->d_xpack;
-    {
-        ig_prof_scope prof(ctx, "pack_panel", (double)nxrows * 512.0 * 2.0);
-        int64_t gt = (nxrows + 63) / 64;
-        const int64_t cap = (int64_t)ctx->num_cu * 16;
-        if (gt > cap) gt = cap;
-        hipLaunchKernelGGL(k_pack_panel_tiled<64>, dim3((unsigned)gt), dim3(BLK), 0, ctx->stream, nxrows, (int64_t)64, (const float2*)X, ldx, xp, xrows);
-        IG_LAUNCH_CHECK(ctx, "k_pack_panel_tiled");
-    }
-    const float2 alpha = make_float2(ar, ai), beta = make_float2(br, bi);
-    const bool b0 = br == 0.f && bi == 0.f;
-    const unsigned blocks = (unsigned)((M + 63) / 64);
-    ig_prof_scope prof(ctx, "csrmm_runs");
-#define IG_RUNS(BM_, RW_) hipLaunchKernelGGL((k_csrmm_runs64r<BM_, RW_>), dim3(blocks), dim3(256), 0, ctx->stream, M, rowptr, run_dptr, dcols, \
-                                             (const RunEntry*)entries, run_order, (const float2*)xp, (float2*)Y, ldy, alpha, beta)
-    if (b0) { if (all_real) IG_RUNS(0, true); else IG_RUNS(0, false); }
-    else    { if (all_real) IG_RUNS(1, true); else IG_RUNS(1, false); }
-#undef IG_RUNS
-    IG_LAUNCH_CHECK(ctx, "k_csrmm_runs64r");
-    return IG_OK;
-}
+// ---- host-side structure analysis -------------------------------------------
 
 int ig_csr_inspect(const int32_t* rowptr, const int32_t* colind, int64_t M, int64_t K,
                    int64_t* nzrow, int64_t* nzcol, int* exwrite) {

@@ -448,6 +448,13 @@ def test_csrmm_strided_panels_and_complex_scalars(hip):
         exp = Xbig.copy()
         exp[2:2 + K] = beta * Xbig[2:2 + K] + alpha * (A.conj().T @ Ybig[4:4 + M])
         np.testing.assert_allclose(Yd.to_host(), exp, atol=1e-5)
+        # beta == 0 into a NaN-filled row-slice: the result is written without being read (the scatter's zeroing pre-pass over a
+        # panel whose leading dimension exceeds its rows), and nothing outside the slice is touched
+        Yd = hip.copy_array(np.full((K + 6, n), np.nan, dtype=C64, order='F'))
+        A_d.adjoint(Yd[2:2 + K, :], Xd[4:4 + M, :], alpha=alpha, beta=0)
+        got = Yd.to_host()
+        np.testing.assert_allclose(got[2:2 + K], alpha * (A.conj().T @ Ybig[4:4 + M]), atol=1e-5)
+        assert np.isnan(got[:2]).all() and np.isnan(got[2 + K:]).all()
     hip.adjoint_policy = "transpose"
 
 
@@ -954,6 +961,9 @@ def test_real_weight_formats_of_a_gridding_matrix(hip, monkeypatch, N, residue):
             A_d.forward(k_d, g_d, alpha=1.5)
             assert (A_d._real_values() is not None) == real_entries
             fwd = k_d.to_host()
+            k_d = hip.copy_array(X)                      # the same product on top of a filled result: beta != 0
+            A_d.forward(k_d, g_d, alpha=1.5, beta=0.5j)
+            assert rel_err(k_d.to_host(), 1.5 * (A.astype(np.complex128) @ G.astype(np.complex128)) + 0.5j * X) < RTOL
         return adj, fwd
     adj_r, fwd_r = products(True)
     adj_c, fwd_c = products(False)
