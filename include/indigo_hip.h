@@ -190,7 +190,8 @@ int  ig_permute3_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, const int 
  * soft_threshold).  These have no reference counterpart: the reference's pics has no sparsifying transform.
  * y[:, j] = beta*y[:, j] + alpha * W x[:, j] (inverse != 0: W^H = W^-1) for ncols F-ordered n0 x n1 x n2 columns, every axis
  * <= 1024 long.  wavelet 0 haar, 1 db2, 2 db4 (Daubechies, 2 / 4 / 8 taps); the split rule and the level order are those of
- * DESIGN.md §3.6.  x == y is in place (beta must then be 0).  beta == 0: y is not read.                                     */
+ * DESIGN.md §3.6.  x == y with ldx == ldy is in place (beta must then be 0); any other y that overlaps x is IG_ERR_ARG, with
+ * nothing written.  beta == 0: y is not read.                                                                             */
 int  ig_dwt3_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int wavelet, int levels, int inverse, int64_t ncols,
                  const void* x, int64_t ldx, float alpha_re, float alpha_im, float beta_re, float beta_im,
                  void* y, int64_t ldy);

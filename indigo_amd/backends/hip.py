@@ -799,17 +799,18 @@ class HipBackend(Backend):
                                             ar, ai, br, bi, ctypes.c_void_p(y._arr), y._leading_dim), "ig_permute3_c64")
 
     def dwt3(self, y, x, dims, wavelet, levels, inverse=False, alpha=1, beta=0):
-        """Backend.dwt3 on the device (ig_dwt3_c64): panels of any column count with their leading dimensions; y may be x"""
+        """Backend.dwt3 on the device (ig_dwt3_c64): panels of any column count with their leading dimensions, or the columns
+        stacked in one vector, as the host form takes them; y may be x"""
         assert x.dtype == _C64 and y.dtype == _C64, "only complex64 is supported"
         n0, n1, n2 = (int(n) for n in dims)
         n = n0 * n1 * n2
-        assert x.shape[0] == n and y.shape[0] == n and x.size == y.size, (x.shape, y.shape, dims)
-        ncols = x.shape[1] if x.ndim == 2 else 1
+        assert n > 0 and x.size % n == 0 and x.size == y.size, (x.shape, y.shape, dims)
+        ncols = x.size // n
+        (xp, ldx), (yp, ldy) = self._frame_panel(x, n, ncols), self._frame_panel(y, n, ncols)
         ar, ai = _cplx(alpha)
         br, bi = _cplx(beta)
         self._check(self._L.ig_dwt3_c64(self._ctx, n0, n1, n2, WAVELET_IDS[wavelet], int(levels), int(bool(inverse)), ncols,
-                                        ctypes.c_void_p(x._arr), x._leading_dim, ar, ai, br, bi,
-                                        ctypes.c_void_p(y._arr), y._leading_dim), "ig_dwt3_c64")
+                                        xp, ldx, ar, ai, br, bi, yp, ldy), "ig_dwt3_c64")
 
     def soft_threshold(self, x, tau, dims, keep):
         """Backend.soft_threshold on the device (ig_csoft_c64), in place"""

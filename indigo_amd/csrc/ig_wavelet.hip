@@ -250,6 +250,8 @@ int ig_dwt3_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int wavelet, in
     const bool b0 = (br == 0.f && bi == 0.f);
     IG_REQUIRE(ctx, b0 || x != y, "ig_dwt3_c64: beta != 0 needs y distinct from x");
     IG_REQUIRE(ctx, x != y || ldx == ldy, "ig_dwt3_c64: in place with different leading dimensions");
+    IG_REQUIRE(ctx, x == y || !ig_panels_overlap(x, ldx, vol, ncols, y, ldy, vol, ncols),
+               "ig_dwt3_c64: y overlaps x (y == x with ldy == ldx is the in-place form)");
     if (int rc = ig_set_device(ctx)) return rc;
     const int64_t n[3] = {n0, n1, n2};
     const float2 a = make_float2(ar, ai), one = make_float2(1.f, 0.f);

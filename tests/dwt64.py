@@ -79,6 +79,56 @@ def dwt(x, dims, wavelet, levels, inverse=False):
     return v.reshape(x.shape, order='F')
 
 
+def dwt_abs(a, dims, wavelet, levels, inverse=False):
+    """the same passes with |M| in place of every analysis matrix, on a non-negative real array of the shape `dwt` takes: the
+    magnitudes a transform's roundings scale with.  Every pass of a float32 transform computes an output as TAPS fmas on exact
+    products of rounded filter constants, an error of at most (TAPS + 2) 2^-24 sum_j |M_kj| |v_j|; later passes carry it on through
+    their own |M|, so a whole transform of complex x is elementwise within
+        npasses (TAPS + 2) 2^-24 dwt_abs(|x|)
+    of the exact one (first order in 2^-24; for the moduli of complex values by the triangle inequality)"""
+    a = np.asarray(a, dtype=np.float64)
+    assert (a >= 0).all()
+    cols = a.reshape((int(np.prod(dims)), -1), order='F')
+    v = cols.reshape(tuple(dims) + (cols.shape[1],), order='F').copy()
+    h = daubechies(TAPS[wavelet])
+    plan, _ = passes(dims, wavelet, levels)
+    for box, ax in (reversed(plan) if inverse else plan):
+        M = abs(analysis_matrix(box[ax], h))
+        _apply(v, box, ax, M.T if inverse else M)
+    return v.reshape(a.shape, order='F')
+
+
+U32 = 2.0 ** -24                                                   # the unit roundoff of float32
+
+
+def dwt_bound(x, dims, wavelet, levels, inverse=False, alpha=1, beta=0, y0=None):
+    """elementwise bound on |y - (alpha T x + beta y0)| for y = ig_dwt3_c64's float32 result, T = W or W^T (see dwt_abs).
+    beta == 0: the passes, and one complex multiply by alpha when alpha != 1 (two roundings per component, 2 sqrt(2) < 3 for the
+    modulus).  beta != 0: the kernel computes T (beta T^H y0 + alpha x) in three stages, whose errors add up."""
+    per_transform = len(passes(dims, wavelet, levels)[0]) * (TAPS[wavelet] + 2) * U32
+    ax = abs(alpha) * np.abs(np.asarray(x, dtype=np.complex128))
+    if beta == 0:
+        scaling = 0.0 if alpha == 1 else 3 * U32
+        return (per_transform + scaling) * dwt_abs(ax, dims, wavelet, levels, inverse)
+    thy = dwt(y0, dims, wavelet, levels, not inverse)              # T^H y0
+    z1, z2 = np.abs(thy), np.abs(beta * thy + alpha * np.asarray(x, dtype=np.complex128))
+    # stage 1, z1 = T^H y0 in place: the passes of the opposite direction; the combine then multiplies what they left by beta
+    e1 = abs(beta) * per_transform * dwt_abs(np.abs(np.asarray(y0, dtype=np.complex128)), dims, wavelet, levels, not inverse)
+    # stage 2, z2 = alpha x + beta z1: a complex multiply (2 roundings per component) and two fmas per component on top of it,
+    # each rounding a partial sum of at most |alpha x| + |beta z1|: 4 roundings per component, 4 sqrt(2) < 6 for the modulus
+    e2 = 6 * U32 * (ax + abs(beta) * z1)
+    # stage 3, T z2 in place: carries e1 + e2 through |T| and adds its own passes' roundings
+    return dwt_abs(e1 + e2, dims, wavelet, levels, inverse) + per_transform * dwt_abs(z2, dims, wavelet, levels, inverse)
+
+
+def worst_ratio(err, bound):
+    """max of err / bound; where the bound is 0 (an exact operation) any error at all is infinitely far out"""
+    err, bound = np.asarray(err, dtype=np.float64), np.asarray(bound, dtype=np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        r = np.where(bound > 0, err / bound, np.where(err > 0, np.inf, 0.0))
+    return float(r.max()) if r.size else 0.0
+
+
 def dense(dims, wavelet, levels):
     """the transform's N x N matrix"""
     n = int(np.prod(dims))

@@ -8,9 +8,10 @@ import numpy as np
 import pytest
 
 import dwt64
+import dwt_cases
 from conftest import check_misc_leaves
 from indigo_amd import pics
-from indigo_amd.backends.backend import WAVELETS, dwt_coarse_box
+from indigo_amd.backends.backend import WAVELETS, dwt_coarse_box, dwt_plan
 from indigo_amd.sense import radial_trajectory
 from indigo_amd.util import rand64c
 
@@ -235,3 +236,162 @@ def test_pics_l1_matches_a_float64_fista(scan16, oracle_backend, caplog):
     oracle_backend._scratch = None
     est = [r.getMessage() for r in caplog.records if "largest eigenvalue" in r.getMessage()]
     assert est and abs(float(est[0].split("lamda I ")[1].split()[0]) - lam) < 1e-2 * lam
+
+
+# ---- the case table of the GPU tests (tests/dwt_cases.py) and the elementwise bound they use (dwt64.dwt_bound) ----------------
+
+def test_the_case_table_reaches_what_it_claims():
+    """from dwt64.passes: the empty plans, the first passes on another axis than 0, the strips above 64 KB of LDS and the lines of
+    every pass's last group"""
+    geo = {dwt_cases.case_id(c): dwt_cases.launches(*c) for c in dwt_cases.CASES}
+    assert len(geo) == len(dwt_cases.CASES)                                # the ids are distinct
+    assert sorted(k for k, g in geo.items() if not g) == ["16x16x16_db2_0", "2x2x2_haar_1", "7x9x5_db2_3"]
+    first = {k: g[0][0] for k, g in geo.items() if g}
+    assert {k: a for k, a in first.items() if a != 0} == {"9x16x4_db2_3": 1, "1x1x64_db4_5": 2, "12x16x3_db4_2": 1,
+                                                          "41x4x6_haar_2": 1, "5x4x1024_db4_9": 2}
+    # (axis, d, LDS bytes) of every pass that has to ask for more than 64 KB: 65 536 itself (d = 512) does not
+    big = {k: [(a, d, lds) for a, d, _, _, _, lds, _ in g if lds > dwt_cases.LDS_DEFAULT] for k, g in geo.items()}
+    assert {k: v for k, v in big.items() if v} == {"20x640x3_db4_2": [(1, 640, 81920)], "5x4x1024_db4_9": [(2, 1024, 131072)]}
+    assert (2, 512, 65536) in [(a, d, lds) for a, d, _, _, _, lds, _ in geo["5x4x1024_db4_9"]]
+    assert max(lds for g in geo.values() for *_, lds, _ in g) <= 160 * 1024
+    # passes, and for each (axis, lines P, lines of the last group)
+    lines = {k: [(a, P, last) for a, _, P, _, _, _, last in g] for k, g in geo.items()}
+    assert lines["9x16x4_db2_3"] == [(1, 9, 9), (1, 9, 9)]
+    assert lines["12x10x3_haar_3"] == [(0, 10, 10), (1, 6, 6), (0, 5, 5)]
+    assert lines["16x8x1_db2_3"] == [(0, 8, 8), (1, 8, 8), (0, 4, 4)]
+    assert lines["1x1x64_db4_5"] == [(2, 1, 1)] * 3 and dwt64.coarse_box((1, 1, 64), "db4", 5) == (1, 1, 8)
+    assert lines["40x6x34_haar_2"] == [(0, 6, 6), (1, 20, 4), (2, 20, 4), (0, 3, 3)]
+    assert dwt64.coarse_box((40, 6, 34), "haar", 2) == (10, 3, 17)
+    assert lines["12x16x3_db4_2"] == [(1, 12, 12)]
+    assert lines["41x4x6_haar_2"] == [(1, 41, 9), (2, 41, 9)]
+    assert lines["48x20x24_db4_3"] == [(0, 20, 4), (1, 24, 8), (2, 24, 8), (0, 10, 10)]
+    assert lines["20x640x3_db4_2"] == [(0, 640, 16), (1, 10, 10), (1, 10, 10)]
+    assert lines["5x4x1024_db4_9"] == [(2, 5, 5)] * 7
+    assert lines["1024x4x2_db2_9"] == [(0, 4, 4)] * 8 and geo["1024x4x2_db2_9"][0][4] == 4      # W = 4 lines at d = 1024
+    dims, wavelet, levels, ncols = dwt_cases.MANY_COLUMNS
+    assert ncols > 65535 and len(dwt64.passes(dims, wavelet, levels)[0]) == 3
+    for dims, wavelet, levels in dwt_cases.CASES:                          # the product's plan is the restatement's
+        assert dwt_plan(dims, wavelet, levels) == dwt64.passes(dims, wavelet, levels)
+
+
+@pytest.mark.parametrize("case", dwt_cases.CASES, ids=dwt_cases.case_id)
+def test_host_forms_match_the_float64_transform_on_the_case_table(oracle_backend, case):
+    B = oracle_backend
+    dims, wavelet, levels = case
+    n = int(np.prod(dims))
+    x, y0 = dwt_cases.make_input(dims, 2, seed=1), dwt_cases.make_input(dims, 2, seed=9)
+    for inverse in (False, True):
+        ref = dwt64.dwt(x, dims, wavelet, levels, inverse=inverse)
+        y = B.copy_array(np.full((n, 2), np.nan, dtype=C64, order='F'))
+        B.dwt3(y, B.copy_array(x), dims, wavelet, levels, inverse=inverse)
+        assert _rel(y.to_host(), ref) < 1e-6
+        y = B.copy_array(y0)
+        B.dwt3(y, B.copy_array(x), dims, wavelet, levels, inverse=inverse, alpha=0.5j, beta=2 - 1j)
+        assert _rel(y.to_host(), 0.5j * ref + (2 - 1j) * y0) < 1e-6
+
+
+def _f32(a):
+    return np.asarray(a, dtype=np.float32)
+
+
+def _fma(a, b, c):
+    """float32 fma: the product of two float32 is exact in float64, and the one rounding of the sum to float64 before the rounding
+    to float32 changes the result in no case that matters here"""
+    return _f32(np.float64(a) * np.float64(b) + np.float64(c))
+
+
+def _cmul32(a, vr, vi):
+    """ig_common.h's cmul(a, v): (fma(a.x, v.x, -(a.y v.y)), fma(a.x, v.y, a.y v.x))"""
+    ar, ai = np.float32(a.real), np.float32(a.imag)
+    return _fma(ar, vr, -(ai * vi)), _fma(ar, vi, ai * vr)
+
+
+def _emulate_split(v, h, inverse):
+    """one split along axis 0 of the float32 array v, tap by tap in the order of k_dwt_lines"""
+    taps, d = h.size, v.shape[0]
+    half = d // 2
+    g = _f32([(-1.0 if j & 1 else 1.0) * h[taps - 1 - j] for j in range(taps)])
+    out = np.zeros_like(v)
+    k = np.arange(half)
+    if not inverse:
+        for t in range(taps):
+            src = v[(2 * k + t) % d]
+            out[:half] = _fma(h[t], src, out[:half])
+            out[half:] = _fma(g[t], src, out[half:])
+    else:
+        for t in range(taps // 2):
+            m = (k - t) % half
+            lo, hi = v[m], v[half + m]
+            for r in (0, 1):
+                out[r::2] = _fma(h[2 * t + r], lo, out[r::2])
+                out[r::2] = _fma(g[2 * t + r], hi, out[r::2])
+    return out
+
+
+def _emulate(x, dims, wavelet, levels, inverse, alpha=1):
+    """alpha * T x in float32 the way ig_wavelet.hip's transform() goes about it: forward, alpha rides on the first pass's outputs;
+    inverse (or no pass), a scaling pass comes first"""
+    h = _f32(WAVELETS[wavelet])
+    plan = dwt64.passes(dims, wavelet, levels)[0]
+    v = [np.array(p, dtype=np.float32).reshape(tuple(dims) + (-1,), order='F') for p in (x.real, x.imag)]
+    if alpha != 1 and (inverse or not plan):
+        v = list(_cmul32(alpha, *v))
+    for i, (box, a) in enumerate(reversed(plan) if inverse else plan):
+        sl = tuple(slice(0, c) for c in box)
+        new = [np.moveaxis(_emulate_split(np.moveaxis(p[sl], a, 0), h, inverse), 0, a) for p in v]
+        if alpha != 1 and not inverse and i == 0:
+            new = _cmul32(alpha, *new)
+        for p, q in zip(v, new):
+            p[sl] = q
+    return (v[0] + 1j * v[1]).reshape(x.shape, order='F')
+
+
+@pytest.mark.parametrize("case", dwt_cases.CASES, ids=dwt_cases.case_id)
+def test_a_float32_transform_stays_inside_the_elementwise_bound(case):
+    """a plain numpy float32 restatement of the kernel's arithmetic (not the backend's host form, which computes in float64) against
+    dwt64.dwt_bound: the bound the GPU tests use is attainable, with room, by a correct float32 transform"""
+    dims, wavelet, levels = case
+    x, y0 = dwt_cases.make_input(dims, dwt_cases.NCOLS, seed=1), dwt_cases.make_input(dims, dwt_cases.NCOLS, seed=2)
+    alpha, beta = 0.75 - 0.5j, -0.25 + 1.5j
+    worst = 0.0
+    for inverse in (False, True):
+        ref = dwt64.dwt(x, dims, wavelet, levels, inverse)
+        for a in (1, alpha):
+            err = np.abs(_emulate(x, dims, wavelet, levels, inverse, a) - a * ref)
+            bound = dwt64.dwt_bound(x, dims, wavelet, levels, inverse, alpha=a)
+            assert (bound > 0).all() or (a == 1 and not bound.any())       # alpha == 1 and no pass: an exact copy
+            assert (err <= bound).all(), (inverse, a, dwt64.worst_ratio(err, bound))
+            worst = max(worst, dwt64.worst_ratio(err, bound))
+        # beta != 0: T (beta T^H y0 + alpha x), the combining pass as k_dwt_combine has it
+        z = _emulate(y0, dims, wavelet, levels, not inverse)
+        rr, ri = _cmul32(alpha, _f32(x.real), _f32(x.imag))
+        br, bi = np.float32(beta.real), np.float32(beta.imag)
+        rr, ri = _fma(-bi, _f32(z.imag), _fma(br, _f32(z.real), rr)), _fma(bi, _f32(z.real), _fma(br, _f32(z.imag), ri))
+        out = _emulate(np.asfortranarray(rr + 1j * ri), dims, wavelet, levels, inverse)
+        err = np.abs(out - (alpha * ref + beta * y0))
+        bound = dwt64.dwt_bound(x, dims, wavelet, levels, inverse, alpha=alpha, beta=beta, y0=y0)
+        assert (err <= bound).all(), (inverse, "beta", dwt64.worst_ratio(err, bound))
+        worst = max(worst, dwt64.worst_ratio(err, bound))
+    print("%s: worst error / bound %.3f" % (dwt_cases.case_id(case), worst))
+    assert worst < 0.5                                                     # a correct transform leaves a margin of two at least
+
+
+def test_the_bound_on_unit_vectors_rejects_a_wrong_tap():
+    """the last db4 tap (0.0106 of the largest) off by a relative 2^-18, 64 float32 roundings: on dense data that is less than one
+    rounding of an output and no bound can see it; on unit vectors every coefficient is a product of single taps, the bound is
+    relative to each of them, and the wrong tap leaves it -- which is why the GPU tests transform the unit vectors too"""
+    dims, wavelet, levels = (1, 1, 64), "db4", 5
+    h = dwt64.daubechies(8)
+    h[-1] *= 1 + 2.0 ** -18
+    wrong = np.eye(64)
+    for box, a in dwt64.passes(dims, wavelet, levels)[0]:
+        wrong[:box[a]] = dwt64.analysis_matrix(box[a], h) @ wrong[:box[a]]
+    assert np.abs(wrong - dwt64.dense(dims, wavelet, levels)).max() < 1e-7
+    eye = np.asfortranarray(np.eye(64, dtype=C64))
+    bound = dwt64.dwt_bound(eye, dims, wavelet, levels)
+    assert dwt64.worst_ratio(np.abs(wrong - dwt64.dense(dims, wavelet, levels)), bound) > 4
+    dense_x = dwt_cases.make_input(dims, 1, seed=1)
+    err = np.abs(wrong @ dense_x.astype(np.complex128) - dwt64.dwt(dense_x, dims, wavelet, levels))
+    assert dwt64.worst_ratio(err, dwt64.dwt_bound(dense_x, dims, wavelet, levels)) < 0.1
+    out = _emulate(eye, dims, wavelet, levels, False)                      # and the float32 transform itself stays inside
+    assert dwt64.worst_ratio(np.abs(out - dwt64.dense(dims, wavelet, levels)), bound) < 0.5
