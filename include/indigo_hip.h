@@ -362,6 +362,43 @@ int  ig_coil_gram_c64(ig_ctx* ctx, int64_t n, int64_t nc, const void* x, int64_t
  * One pass: 8 nk + 12 bytes per voxel (the dictionary, 8 nk na bytes, stays in the L2), 8 nk na real flops per voxel.            */
 int  ig_dict_match_c64(ig_ctx* ctx, int64_t n, int64_t nk, int64_t na, const void* x, int64_t ldx, const void* d, int64_t ldd,
                        int32_t* idx, void* ip);
+/* Density compensation (indigo_amd.dcf, Backend.dcf_spread / dcf_gather_div / row_scale, pics --dcf).  No reference
+ * counterpart.  The two halves of one Pipe-Menon iteration w <- w / (G G^H w) on ONE real column, G the gridding matrix of M samples
+ * on the n0 x nm x ns grid in the separable form of ig_interp3_sep: `records` (device) built WITHOUT modulation and with scale 1, so
+ * that the taps are the plain positive weights, tw = 4, 6 or 8, rec_stride >= ig_interp3_sep_words(tw) 32-bit words from one record
+ * to the next.  A tap is the float32 product (w1 * w2) * w0 of its axis weights (two roundings, no fused multiply-add); taps beyond
+ * an axis's tap count are skipped.  `order` (device, M uint32) lists the samples binned by the 16 x 8 x 8 tile of the grid
+ * (tile = t0 + ceil(n0 / 16) * (t1 + ceil(nm / 8) * t2)) in which their wrapped first tap lies; grid dimensions need not be
+ * multiples of the tile.  Every axis holds between tw and 65535 cells, M < 2^32 and scale is a positive power of two, else
+ * IG_ERR_UNSUPPORTED / IG_ERR_ARG with nothing written.
+ * ig_dcf_spread_r32: acc = G^H w in fixed point.  acc (device, n0 nm ns int64, first axis fastest) is zeroed by the call; every tap
+ *   then adds  llrint(tap * w[i] * scale)  -- the product formed in double, where it is exact, rounded to nearest-even once -- as a
+ *   64-bit integer.  The caller picks scale so that M * max(w) * scale <= 2^62: taps are <= 1, nothing overflows.  Integer addition
+ *   is associative: acc does not depend on the order in which the adds arrive, is bitwise repeatable, and carries an error of at
+ *   most half a quantum per contribution however many samples share a cell.  One workgroup per non-empty tile: tile_ids (device,
+ *   ntiles int32) and tile_ptr (device, ntiles + 1 int64): the samples of tile_ids[k] are order[tile_ptr[k] .. tile_ptr[k + 1]); a
+ *   heavy tile may be listed several times, each entry with a piece of its samples and a workgroup of its own.  An entry
+ *   of at least lds_min samples sums into an LDS image of the tile plus a halo of tw - 1 cells per axis (41 KB at tw = 8) and
+ *   adds the image's non-zero cells to acc modulo the grid dimensions; a tile below lds_min adds straight to acc.  Both routes use
+ *   plain 64-bit atomic adds and give the same bits: lds_min (0: every tile through LDS; 2^31: none) only tunes.  w (device, M
+ *   float32) is not written.  4 rec_stride + 4 bytes read and up to 8 tw^3 bytes of atomics per sample.
+ * ig_dcf_gather_div_r32: s_i = sum_taps tap * (double)acc[cell] / scale, summed in double; w_out[i] = (float)(w[i] / s_i), or 0 where
+ *   s_i == 0; s_out (optional, NULL: not wanted) [i] = (float)s_i.  maxima (device, 2 float32) receives max_i w_out[i] and
+ *   max_i |s_i - 1| (the latter rounded to float32 once), both through atomicMax on the bit patterns of non-negative floats:
+ *   independent of the order.  The samples are visited in `order`, so consecutive workgroups read the same rows of acc.  w_out may
+ *   be w; any other overlap among w, w_out and s_out is IG_ERR_ARG.  acc is not written.
+ * ig_rowscale_r32_c64: Y[i, c] = w[i] * X[i, c] for i < n, c < ncols: the diagonal of a weighted data term, one real float32 weight
+ *   per row shared by all columns (operators.SampleWeights).  X and Y are device column-major complex64 panels, ldx, ldy >= n in
+ *   elements; rows between the columns are never touched.  One float32 product per component: exact against w.astype(float32) * x.
+ *   Y == X with ldy == ldx is the in-place form; any other overlap of Y with X or w is IG_ERR_ARG, with nothing written.  n >= 1 and
+ *   ncols >= 1, else IG_ERR_UNSUPPORTED.  One pass: 16 n ncols + 4 n bytes.                                                       */
+int  ig_dcf_spread_r32(ig_ctx* ctx, int64_t M, int tw, const uint32_t* records, int64_t rec_stride, const uint32_t* order,
+                       const int64_t* tile_ptr, const int32_t* tile_ids, int64_t ntiles, const float* w, double scale, int64_t lds_min,
+                       int64_t* acc, int64_t n0, int64_t nm, int64_t ns);
+int  ig_dcf_gather_div_r32(ig_ctx* ctx, int64_t M, int tw, const uint32_t* records, int64_t rec_stride, const uint32_t* order,
+                           const int64_t* acc, int64_t n0, int64_t nm, int64_t ns, double scale, const float* w, float* w_out,
+                           float* s_out, float* maxima);
+int  ig_rowscale_r32_c64(ig_ctx* ctx, int64_t n, int64_t ncols, const float* w, const void* x, int64_t ldx, void* y, int64_t ldy);
 
 /* ------------------------------------------------------------------------
  * CSR x dense-panel SpMM.  Replaces Backend.ccsrmm

@@ -66,7 +66,7 @@ class Memusage(Visitor):
             if id(node) not in self._seen:
                 self._seen.add(id(node))
                 self._base += (node.shape[0] + 1) * 4 + node.nnz * 4 + node.nnz * 8
-        elif isinstance(node, (op.DenseMatrix, op.FrameBasis, op.CoilMaps, op.SegmentPhase, op.SegmentCombine)):
+        elif isinstance(node, (op.DenseMatrix, op.FrameBasis, op.CoilMaps, op.SegmentPhase, op.SegmentCombine, op.SampleWeights)):
             if id(node) not in self._seen:
                 self._seen.add(id(node))
                 self._base += node._matrix.nbytes

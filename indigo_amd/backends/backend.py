@@ -1006,6 +1006,94 @@ class Backend(object):
         return idx, ip
 
     @staticmethod
+    def _dcf_taps(rec, tw, dims):
+        """(cells, taps) of the separable records `rec` (rows of at least 3 tw + 2 words), each (rows, tw^3): the grid cell of every
+        tap in the records' memory order and its value in the kernels' float32 arithmetic, (w1 * w2) * w0; taps beyond an axis's
+        tap count are 0 (their cells are valid: they add nothing)"""
+        n0, nm, ns = (int(n) for n in dims)
+        wts = np.ascontiguousarray(rec[:, :3 * tw]).view(np.float32).reshape(-1, 3, tw)
+        h0, h1 = rec[:, 3 * tw].astype(np.int64), rec[:, 3 * tw + 1].astype(np.int64)
+        a = np.arange(tw)
+        cell, val = [], []
+        for axis, (first, count, n) in enumerate(((h0 & 0xffff, (h1 >> 16) & 15, n0), (h0 >> 16, (h1 >> 20) & 15, nm), (h1 & 0xffff, (h1 >> 24) & 15, ns))):
+            cell.append((first[:, None] + a) % n)
+            val.append(np.where(a < count[:, None], wts[:, axis], np.float32(0)).astype(np.float32))
+        cells = cell[0][:, None, None, :] + n0 * (cell[1][:, None, :, None] + nm * cell[2][:, :, None, None])
+        taps = (val[1][:, None, :, None] * val[2][:, :, None, None]).astype(np.float32) * val[0][:, None, None, :]
+        return cells.reshape(rec.shape[0], -1), taps.astype(np.float32).reshape(rec.shape[0], -1)
+
+    @staticmethod
+    def _dcf_records(records, sep, M):
+        rec = records.to_host().reshape(-1)
+        stride = int(sep.get('stride') or rec.size // max(M, 1))
+        assert stride >= 3 * sep['tw'] + 2 and rec.size >= M * stride, (rec.size, M, stride)
+        return rec[:M * stride].reshape(M, stride)
+
+    def dcf_spread(self, acc, w, records, sep, scale, tiles):
+        """acc = G^H w in fixed point, the first half of a Pipe-Menon iteration (indigo_amd.dcf).  G is the gridding
+        matrix in separable form: `records` a backend uint32 array of the records of `interp.interp_sep_records` built with
+        phases=None and scale=1, `sep` its description (tw, dims = the grid in memory order, optional stride = words from one
+        record to the next).  w: M float32 weights.  acc: int64 over the grid, zeroed here; every tap adds
+        rint(tap * w[i] * scale) with the product formed in float64, where it is exact; scale a power of two with
+        M * max(w) * scale <= 2^62.  Integer sums do not depend on the order of the adds: the result is the same bits on every
+        backend and route.  tiles: the samples binned by grid tile (`grid_formats.dcf_tiles`, as backend arrays) -- how a device
+        backend divides the work; without meaning here.  Host form through to_host / copy_from; device backends override it."""
+        M = int(w.size)
+        tw, dims = int(sep['tw']), tuple(int(n) for n in sep['dims'])
+        e = np.frexp(float(scale))
+        if not (scale > 0 and e[0] == 0.5):
+            raise RuntimeError("dcf_spread: scale %r is no positive power of two" % (scale,))
+        assert acc.dtype == np.dtype('int64') and acc.size == int(np.prod(dims)), (acc.shape, dims)
+        rec = self._dcf_records(records, sep, M)
+        wv = w.to_host().reshape(-1).astype(np.float64) * float(scale)
+        out = np.zeros(acc.size, dtype=np.int64)
+        for lo in range(0, M, 4096):
+            cells, taps = self._dcf_taps(rec[lo:lo + 4096], tw, dims)
+            np.add.at(out, cells.reshape(-1), np.rint(taps.astype(np.float64) * wv[lo:lo + 4096, None]).astype(np.int64).reshape(-1))
+        acc.copy_from(np.asfortranarray(out.reshape(acc.shape, order='F')))
+
+    def dcf_gather_div(self, w_out, acc, w, records, sep, scale, tiles, s_out=None):
+        """The second half of a Pipe-Menon iteration: s_i = sum_taps tap * float64(acc[cell]) / scale in float64 and
+        w_out[i] = float32(w[i] / s_i), 0 where s_i == 0; s_out (optional) [i] = float32(s_i).  Arguments as for `dcf_spread`, whose
+        acc this reads; w_out may be w.  Returns (max_i w_out[i], max_i |s_i - 1| rounded to float32) as floats: the next
+        iteration's scale and the log line.  Host form through to_host / copy_from; device backends override it."""
+        M = int(w.size)
+        tw, dims = int(sep['tw']), tuple(int(n) for n in sep['dims'])
+        rec = self._dcf_records(records, sep, M)
+        a = acc.to_host().reshape(-1).astype(np.float64)
+        wv = w.to_host().reshape(-1).astype(np.float64)
+        s = np.zeros(M)
+        for lo in range(0, M, 4096):
+            cells, taps = self._dcf_taps(rec[lo:lo + 4096], tw, dims)
+            s[lo:lo + 4096] = (taps.astype(np.float64) * a[cells]).sum(axis=1)
+        s /= float(scale)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            q = np.where(s == 0, 0.0, wv / s).astype(np.float32)
+        w_out.copy_from(np.asfortranarray(q.reshape(w_out.shape, order='F')))
+        if s_out is not None:
+            s_out.copy_from(np.asfortranarray(s.astype(np.float32).reshape(s_out.shape, order='F')))
+        return (float(q.max()), float(np.float32(np.abs(s - 1.0).max()))) if M else (0.0, 0.0)
+
+    def row_scale(self, y, x, w, n, ncols):
+        """y[i, c] = w[i] * x[i, c] for the n x ncols complex64 panels x and y (with their leading dimensions, or the same data
+        stacked in one column) and the n real float32 weights w shared by all columns: the diagonal of a weighted data term
+        (operators.SampleWeights, pics --dcf).  One float32 product per component.  y may be x.  Host form through
+        to_host / copy_from; device backends override it."""
+        n, C = int(n), int(ncols)
+        assert n >= 1 and C >= 1 and w.size == n and x.size == n * C and y.size == n * C, (x.shape, y.shape, w.shape, n, C)
+        wv = w.to_host().reshape(-1).astype(np.float32)[:, None]
+        v = x.to_host().reshape((n, C), order='F')
+        out = np.empty((n, C), dtype=_C64)
+        out.real = wv * v.real
+        out.imag = wv * v.imag
+        y.copy_from(np.asfortranarray(out.reshape(y.shape, order='F')))
+
+    def SampleWeights(self, w, n, ncols, **kwargs):
+        """the real diagonal diag(w) (x) I over `ncols` columns of `n` samples each, shape (n ncols, n ncols): one weight per sample,
+        shared by the coils (see operators.SampleWeights); .H is itself"""
+        return op.SampleWeights(self, w, n, ncols, **kwargs)
+
+    @staticmethod
     def psf_unpack(kern, n, K):
         """the (n, K, K) complex128 Hermitian matrices of a `psf_mix` kernel array: K^2 planes of n floats, the K real diagonals,
         then re and im of every pair (k < k'), the pairs in row-major order of the upper triangle"""

@@ -74,7 +74,11 @@ class HipBackend(Backend):
                            separable=True, sep_gather=True, sep_scatter=True, shares=(4, 8), shares_min_tw=6, share_shape={8: (4, 4, 128, 1024), 4: (4, 4, 128, 1024)},
                            # samples per partial sum of coil_gram: a float32 chain of gram_slab / 8 = 2048 samples per wave (/ 4 beyond 32 coils), 1024 workgroups
                            # and 17 MB of partial sums at 2^24 samples x 64 coils
-                           gram_slab=16384)
+                           gram_slab=16384,
+                           # samples from which a 16 x 8 x 8 tile of the Pipe-Menon spread sums in LDS before it touches the grid (ig_dcf_spread_r32;
+                           # 0: every tile, 2^31: none; the same bits for every value: DESIGN.md §3.17)
+                           # dcf_piece: samples per workgroup of a heavier tile (grid_formats.dcf_tiles)
+                           dcf_lds_min=8, dcf_piece=2048)
 
     def __del__(self):
         try:
@@ -1010,6 +1014,60 @@ class HipBackend(Backend):
         self._check(self._L.ig_dict_match_c64(self._ctx, n, K, N, xp, ldx, ctypes.c_void_p(atoms._arr), atoms._leading_dim,
                                               ctypes.c_void_p(idx._arr), ctypes.c_void_p(ip._arr)), "ig_dict_match_c64")
         return idx.to_host().ravel(), ip.to_host().ravel()
+
+    def _dcf_args(self, what, w, records, sep, tiles):
+        """(M, tw, records, stride, order) of the Pipe-Menon kernels' common arguments, checked"""
+        f32, u32 = np.dtype('float32'), np.dtype('uint32')
+        M, tw = int(w.size), int(sep['tw'])
+        words = int(self._L.ig_interp3_sep_words(tw))
+        stride = int(sep.get('stride') or words)
+        assert w.dtype == f32 and w.contiguous, "%s: the weights are a contiguous float32 array" % what
+        assert records.dtype == u32 and records.contiguous and records.size >= M * stride and stride >= words, (records.shape, M, stride)
+        order = tiles['order']
+        assert order.dtype == u32 and order.contiguous and order.size == M, (order.shape, M)
+        return M, tw, ctypes.c_void_p(records._arr), stride, ctypes.c_void_p(order._arr)
+
+    def dcf_spread(self, acc, w, records, sep, scale, tiles):
+        """Backend.dcf_spread on the device (ig_dcf_spread_r32): one workgroup per non-empty tile of `tiles`; tiles of at least
+        tuning['dcf_lds_min'] samples sum in LDS first, the others add straight to acc.  The same bits either way."""
+        M, tw, rp, stride, op_ = self._dcf_args("dcf_spread", w, records, sep, tiles)
+        dims = tuple(int(n) for n in sep['dims'])
+        assert acc.dtype == np.dtype('int64') and acc.contiguous and acc.size == int(np.prod(dims)), (acc.shape, dims)
+        ptr, ids = tiles['ptr'], tiles['ids']
+        assert ptr.dtype == np.dtype('int64') and ids.dtype == np.dtype('int32') and ptr.contiguous and ids.contiguous, (ptr.dtype, ids.dtype)
+        ntiles = int(ptr.size) - 1 if M else 0
+        assert ids.size >= ntiles, (ids.shape, ptr.shape)
+        lds_min = min(max(int(self.tuning['dcf_lds_min']), 0), 1 << 62)
+        self._check(self._L.ig_dcf_spread_r32(self._ctx, M, tw, rp, stride, op_, ctypes.c_void_p(ptr._arr), ctypes.c_void_p(ids._arr), ntiles,
+                                              ctypes.c_void_p(w._arr), ctypes.c_double(float(scale)), lds_min, ctypes.c_void_p(acc._arr), *dims),
+                    "ig_dcf_spread_r32")
+
+    def dcf_gather_div(self, w_out, acc, w, records, sep, scale, tiles, s_out=None):
+        """Backend.dcf_gather_div on the device (ig_dcf_gather_div_r32): the two maxima come back as 8 bytes"""
+        f32 = np.dtype('float32')
+        M, tw, rp, stride, op_ = self._dcf_args("dcf_gather_div", w, records, sep, tiles)
+        dims = tuple(int(n) for n in sep['dims'])
+        assert acc.dtype == np.dtype('int64') and acc.contiguous and acc.size == int(np.prod(dims)), (acc.shape, dims)
+        assert w_out.dtype == f32 and w_out.contiguous and w_out.size == M, (w_out.shape, M)
+        assert s_out is None or (s_out.dtype == f32 and s_out.contiguous and s_out.size == M), (s_out.shape, M)
+        if getattr(self, '_dcf_maxima', None) is None:
+            self._dcf_maxima = self.zero_array((2,), f32, name='dcf.maxima')
+        mx = self._dcf_maxima
+        self._check(self._L.ig_dcf_gather_div_r32(self._ctx, M, tw, rp, stride, op_, ctypes.c_void_p(acc._arr), *dims, ctypes.c_double(float(scale)),
+                                                  ctypes.c_void_p(w._arr), ctypes.c_void_p(w_out._arr),
+                                                  ctypes.c_void_p(s_out._arr) if s_out is not None else None, ctypes.c_void_p(mx._arr)),
+                    "ig_dcf_gather_div_r32")
+        wmax, dev = mx.to_host()
+        return float(wmax), float(dev)
+
+    def row_scale(self, y, x, w, n, ncols):
+        """Backend.row_scale on the device (ig_rowscale_r32_c64): the panels with their leading dimensions, or stacked in one
+        column; y may be x"""
+        assert x.dtype == _C64 and y.dtype == _C64 and w.dtype == np.dtype('float32'), "complex64 panels and float32 weights"
+        n, C = int(n), int(ncols)
+        assert w.size == n and w.contiguous, (w.shape, n)
+        (xp, ldx), (yp, ldy) = self._frame_panel(x, n, C), self._frame_panel(y, n, C)
+        self._check(self._L.ig_rowscale_r32_c64(self._ctx, n, C, ctypes.c_void_p(w._arr), xp, ldx, yp, ldy), "ig_rowscale_r32_c64")
 
     def psf_mix(self, y, x, kern, n, ncoils, interleaved=False, width=None):
         """Backend.psf_mix on the device (ig_psf_mix_c64): the K images are the columns of panels with their leading

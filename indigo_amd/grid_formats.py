@@ -324,3 +324,32 @@ def gather_order(rec, tw, ncols):
         for a in range(3):
             key |= ((j[a] >> bit) & 1) << (3 * bit + a)
     return np.argsort(key, kind='stable').astype(np.uint32)
+
+
+DCF_TILE = (16, 8, 8)
+
+
+def dcf_tiles(rec, tw, dims, piece=None):
+    """The samples of the separable records `rec` binned for the Pipe-Menon spread (ig_dcf_spread_r32) by the
+    16 x 8 x 8 tile of the grid `dims` (memory order; need not be multiples of the tile) in which their wrapped first tap lies, tile
+    t0 + ceil(n0 / 16) * (t1 + ceil(nm / 8) * t2): dict(order = the samples sorted by tile (stable: trajectory order inside a tile),
+    uint32; ids = the non-empty tiles, ascending, int32; ptr = int64, len(ids) + 1: the samples of tile ids[k] are
+    order[ptr[k]:ptr[k + 1]]).  A workgroup of the spread sums one tile; the gather and divide visits the samples in the same order.
+    piece: a tile of more samples (the k-space centre of a radial scan puts 3e5 of 2^24 samples on one tile) is listed several times,
+    each entry with at most `piece` consecutive samples of it, so that no workgroup is left with a hundredth of the whole scan; integer
+    sums do not care.  None: every tile once."""
+    n0, nm, ns = (int(n) for n in dims)
+    h0, h1 = rec[:, 3 * tw], rec[:, 3 * tw + 1]
+    t0, t1, t2 = (h0 & 0xffff).astype(np.int64) // DCF_TILE[0], (h0 >> 16).astype(np.int64) // DCF_TILE[1], (h1 & 0xffff).astype(np.int64) // DCF_TILE[2]
+    nt0, nt1 = -(-n0 // DCF_TILE[0]), -(-nm // DCF_TILE[1])
+    tile = t0 + nt0 * (t1 + nt1 * t2)
+    order = np.argsort(tile, kind='stable')
+    ids, counts = np.unique(tile, return_counts=True)
+    ptr = np.zeros(ids.size + 1, dtype=np.int64)
+    np.cumsum(counts, out=ptr[1:])
+    if piece is not None and counts.size and int(counts.max()) > int(piece):
+        pieces = -(-counts // int(piece))
+        within = np.arange(int(pieces.sum()), dtype=np.int64) - np.repeat(np.cumsum(pieces) - pieces, pieces)
+        ptr = np.append(np.repeat(ptr[:-1], pieces) + within * int(piece), ptr[-1])
+        ids = np.repeat(ids, pieces)
+    return dict(order=order.astype(np.uint32), ptr=ptr, ids=ids.astype(np.int32))

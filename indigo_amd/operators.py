@@ -867,6 +867,54 @@ class SegmentCombine(MatrixFreeOperator):
             self._backend.segment_combine(y[:, j:j + 1], x[:, j:j + 1], self._matrix_d, P, self._n, adjoint=not forward, alpha=alpha, beta=beta)
 
 
+class SampleWeights(MatrixFreeOperator):
+    """diag(w) (x) I_ncols, shape (n ncols, n ncols): row i of every one of the `ncols` columns of `n` samples (the coils of a
+    k-space vector stacked coil-major) times the real weight w[i].  Real, diagonal and self-adjoint: .H evaluates the same product.
+    `w` is n real values, rounded to float32 once; n floats on the device where a `Diag` of the same operator would hold
+    n ncols complex values and a CSR index.  With w the square roots of density-compensation weights, SampleWeights * A is the
+    forward model of the weighted data term of pics --dcf.  The weights go to the device once, on first
+    evaluation."""
+
+    def __init__(self, backend, w, n, ncols, **kwargs):
+        try:
+            w = np.asarray(w)
+            if np.iscomplexobj(w):
+                raise TypeError
+            w = np.ascontiguousarray(w.reshape(-1, order='F'), dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError("SampleWeights: the weights must be a real array")
+        self._n, self._ncols = int(n), int(ncols)
+        if self._n < 1 or self._ncols < 1:
+            raise ValueError("SampleWeights: n and ncols must be positive, got %s and %s" % (n, ncols))
+        if w.size != self._n:
+            raise ValueError("SampleWeights: %d weights for n = %d samples" % (w.size, self._n))
+        if not np.isfinite(w).all():
+            raise ValueError("SampleWeights: the weights must be finite")
+        self._matrix = w
+        self._matrix_d = None
+        kwargs.setdefault('name', 'sample weights')
+        super().__init__(backend, shape=(self._n * self._ncols,) * 2, **kwargs)
+
+    def _eval(self, y, x, alpha=1, beta=0, forward=True, left=True):
+        B = self._backend
+        if self._matrix_d is None:
+            self._matrix_d = B.copy_array(self._matrix, name=self._name)
+        trace = getattr(B, 'trace', None)
+        if trace is not None:
+            # a single pass: every element moves once each way (8 B), the weights once per column of x
+            trace.add('row_scale', nbytes=(16 * self._n * self._ncols + 4 * self._n) * x.shape[1] + (0 if beta == 0 else y.nbytes),
+                      nflops=2 * self._n * self._ncols * x.shape[1], shape=x.shape, forward=forward, name=self._name)
+        plain = alpha == 1 and beta == 0
+        for j in range(x.shape[1]):
+            xj, yj = (x, y) if x.shape[1] == 1 else (x[:, j:j + 1], y[:, j:j + 1])
+            if plain:
+                B.row_scale(yj, xj, self._matrix_d, self._n, self._ncols)
+            else:
+                with B.scratch(shape=(self.shape[0], 1)) as tmp:
+                    B.row_scale(tmp, xj, self._matrix_d, self._n, self._ncols)
+                    B.axpby(beta, yj, alpha, tmp)
+
+
 class ToeplitzNormal(MatrixFreeOperator):
     """A^H A of a non-Cartesian SENSE problem -- in a temporal subspace of K coefficient images, or K = 1 for one frame -- as ONE
     Toeplitz operator, shape (N K, N K):

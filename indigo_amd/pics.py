@@ -14,6 +14,7 @@ total-variation primal-dual; time frames one by one or in a temporal subspace; s
     python -m indigo_amd.pics --cc V ... scan.npz                                                (V virtual coils: python -m indigo_amd.cc in passing)
     python -m indigo_amd.pics --fmap B0.npy --dwell 4e-6 [--te 1e-3] [--fmap-segments L] ... scan.npz   (off-resonance correction)
     python -m indigo_amd.pics --fmap B0.npy --times T.npy [--fmap-tol 1e-3] [--toeplitz] ... scan.npz
+    python -m indigo_amd.pics --dcf scan.dcf.npy | auto [--dcf-iters 30] ... scan.npz          (density-compensated data term)
 
 The counterpart of the reference's driver script (examples/pics.py:20-95 arguments, data layout and tree
 construction, :179-233 recipe, normal equations, CG, output): reads `data` (k-space), `maps` (coil sensitivities)
@@ -134,6 +135,20 @@ A^H A + lamda I = lamda I + SegmentPhase^H * ToeplitzNormal(K = L) * SegmentPhas
 NUFFTs of conj(b_l) b_l' (L <= 8).  A field map with several time frames, with `--basis` or with M > 1 sets of maps is refused, as
 is a complex one (R2* decay).  Without a field map the driver runs the code it ran before.
 
+Density compensation.  `--dcf FILE.npy` (what `python -m indigo_amd.dcf scan.npz` writes: real weights with the axes of `traj` without
+the coordinate axis, stored reversed like `traj`; a scan that holds an array `dcf` uses it without the flag) or `--dcf auto` (Pipe-Menon
+weights computed in passing, `--dcf-iters` iterations with the run's `--width` and `--osf`, once per distinct trajectory) solves
+
+    min_x  1/2 ||W^(1/2) (A x - y)||^2 + ...            A <- SampleWeights(sqrt w) * A,   y <- sqrt(w) . y
+
+(`bart pics -p`, sigpy's `dcf`; operators.SampleWeights, `Backend.row_scale`): one real weight per sample, shared by the
+coils.  The 1 / r^2 density of a 3-D radial scan is what the first CG iterations are spent undoing; with the weights the second iteration is
+where the plain run is after three or four.  It is for FEW iterations or a starting image: from about the sixth iteration on the weighted
+run is worse (noise amplification at the sparsely sampled periphery), hence opt-in.  Every solver, `--basis`, `--fmap` and M > 1 sets of
+maps run unchanged on the weighted A and y; with `--toeplitz` the point-spread functions are the adjoint NUFFTs of w in place of ones.
+Weights of another shape than the trajectory's, negative or non-finite weights and all-zero weights are refused.  Without the flag the
+driver runs the code it ran before.
+
 Containers: HDF5 (`.h5`, the reference's format; needs h5py, which this image does not ship) or NumPy `.npz` with
 the same three arrays in the same orientation; the result goes back into the HDF5 file as dataset `rec`, or next to
 an `.npz` input as `<name>.rec.npy`.
@@ -194,6 +209,8 @@ def parse(argv):
     ap.add_argument('--te', type=float, default=None, help='time of the first sample of --dwell in seconds (default 0)')
     ap.add_argument('--fmap-segments', type=int, default=None, help='time segments of --fmap, 1..16 (default: the smallest count that reaches --fmap-tol)')
     ap.add_argument('--fmap-tol', type=float, default=1e-3, help='model error (weighted RMS over the field-map histogram) that the automatic choice of --fmap-segments must reach')
+    ap.add_argument('--dcf', default=None, help='density compensation: sample weights from this .npy file (python -m indigo_amd.dcf writes one; a scan array `dcf` is used without the flag), or `auto`: Pipe-Menon weights computed in passing')
+    ap.add_argument('--dcf-iters', type=int, default=30, help='Pipe-Menon iterations of --dcf auto')
     ap.add_argument('data', nargs='?', default="scan.h5", help='k-space data: HDF5 (data/maps/traj) or .npz; maps may hold M <= 4 sets on the MAPS axis (soft-SENSE)')
     args = ap.parse_args(argv)
     if args.llr > 0 and args.l1 > 0:
@@ -225,10 +242,12 @@ def parse(argv):
                  "of the doubled grid, 137 GB at K = 16 on a 512^3 grid" % args.fmap_segments)
     if not args.fmap_tol > 0:
         ap.error("--fmap-tol must be positive")
+    if args.dcf_iters < 0:
+        ap.error("--dcf-iters must not be negative")
     return args
 
 
-def load_extras(path, names=('fmap', 'times')):
+def load_extras(path, names=('fmap', 'times', 'dcf')):
     """the optional arrays of a scan as stored, {name: array} for those of `names` that the file holds"""
     if path.endswith(".npz"):
         z = np.load(path)
@@ -306,13 +325,41 @@ def subspace_basis(basis, frames, rank=None):
     return np.asfortranarray(phi.astype(np.complex64))
 
 
-def toeplitz_normal(B, mps, distinct, which, phi, lamda, width, osf, recipe=None, segments=None):
+def sample_density(dcf, traj_shape):
+    """the weights of a `--dcf` run, checked: `dcf` real, with the axes of the trajectory `traj_shape` = (3, readout, views[, 1, ..., T])
+    without the first (trailing axes of length 1 do not count), non-negative, finite and not all zero -> float64 (readout views, T')
+    with T' the trajectory's frames, the samples of a frame in the order of the k-space vector"""
+    w = np.asarray(dcf)
+    if np.iscomplexobj(w) or w.dtype.kind not in 'fiub':
+        raise ValueError("--dcf: the weights must be a real array, got dtype %s" % w.dtype)
+
+    def strip(shape):
+        shape = tuple(int(n) for n in shape)
+        while len(shape) > 2 and shape[-1] == 1:
+            shape = shape[:-1]
+        return shape
+    if strip(w.shape) != strip(traj_shape[1:]):
+        raise ValueError("--dcf: the weights have shape %s, the trajectory has %s samples (its axes without the coordinate axis)"
+                         % (tuple(w.shape), tuple(traj_shape[1:])))
+    w = w.astype(np.float64)
+    if not np.isfinite(w).all():
+        raise ValueError("--dcf: the weights are not finite (%d of %d are NaN or infinite)" % (int((~np.isfinite(w)).sum()), w.size))
+    if (w < 0).any():
+        raise ValueError("--dcf: %d of %d weights are negative (their square roots scale the data)" % (int((w < 0).sum()), w.size))
+    if not (w > 0).any():
+        raise ValueError("--dcf: all weights are zero")
+    rows = int(np.prod(traj_shape[1:3]))
+    return w.reshape((rows, -1), order='F')
+
+
+def toeplitz_normal(B, mps, distinct, which, phi, lamda, width, osf, recipe=None, segments=None, density=None):
     """A^H A + lamda I of `reconstruct` in Toeplitz form, with the scratch arena reserved for it.  phi (T x K): one
     `ToeplitzNormal` of K coefficient images; phi None: one `ToeplitzNormal` (K = 1) per distinct trajectory, each + lamda I, under a
     `BlockDiag` over the frames `which`, or alone for one frame.  distinct: the trajectories (3, readout, views) in cycles per pixel;
     recipe: the pass list of the run's own trees, for the set-up transform of `psf_kernel`.
     segments = (Phase, weights), the `SegmentPhase` of a field-map run and the (samples, L) expansion of its interpolator: one
-    `ToeplitzNormal` of the L segments between Phase and Phase^H."""
+    `ToeplitzNormal` of the L segments between Phase and Phase^H.
+    density: one real array of sample weights per distinct trajectory (pics --dcf): A^H W A in place of A^H A."""
     from indigo_amd.operators import ToeplitzNormal
     from indigo_amd.toeplitz import psf_kernel
     from indigo_amd.transforms import reserve_for
@@ -323,14 +370,14 @@ def toeplitz_normal(B, mps, distinct, which, phi, lamda, width, osf, recipe=None
     if segments is not None:
         Phase, weights = segments
         L = weights.shape[1]
-        kern = psf_kernel(B, dims, distinct, which, None, width, osf, order=order, recipe=recipe, sample_weights=weights)
+        kern = psf_kernel(B, dims, distinct, which, None, width, osf, order=order, recipe=recipe, sample_weights=weights, density=density)
         AHA = lamda * B.Eye(N) + Phase.H * B.ToeplitzNormal(dims, maps, kern, L, order=order, name='toeplitz segments') * Phase
         AHA._name = 'SENSE off-resonance (Toeplitz)'
         reserve_for(AHA, 1, slack_products=6)
         return AHA
     if phi is not None:
         K = phi.shape[1]
-        kern = psf_kernel(B, dims, distinct, which, phi, width, osf, order=order, recipe=recipe)
+        kern = psf_kernel(B, dims, distinct, which, phi, width, osf, order=order, recipe=recipe, density=density)
         # (lamda I + T, not T + lamda I: a Sum evaluates its right child first, with the caller's beta, so T runs with beta = 0)
         AHA = lamda * B.Eye(N * K) + B.ToeplitzNormal(dims, maps, kern, K, order=order, name='toeplitz subspace')
         AHA._name = 'SENSE subspace (Toeplitz)'
@@ -338,7 +385,7 @@ def toeplitz_normal(B, mps, distinct, which, phi, lamda, width, osf, recipe=None
         return AHA
     ops = []
     for k, trj3 in enumerate(distinct):
-        kern = psf_kernel(B, dims, [trj3], [0], None, width, osf, order=order, recipe=recipe)
+        kern = psf_kernel(B, dims, [trj3], [0], None, width, osf, order=order, recipe=recipe, density=None if density is None else [density[k]])
         ops.append(lamda * B.Eye(N) + B.ToeplitzNormal(dims, maps, kern, 1, order=order, name='toeplitz'))
         ops[-1]._name = 'SENSE (Toeplitz)'
     AHA = ops[0] if len(which) == 1 else B.BlockDiag([ops[k] for k in which], name='SENSE frames (Toeplitz)')
@@ -550,7 +597,7 @@ def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', le
 def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, width=3, fuse=True,
                 l1=0.0, wavelet='db2', levels=3, power_iters=15, step=None, tv=0.0, tv_sigma=None, tv_time=0.0,
                 llr=0.0, llr_block=8, llr_shifts=False, llr_seed=0, basis=None, basis_rank=None, toeplitz=False,
-                fmap=None, times=None, fmap_segments=None, fmap_tol=1e-3):
+                fmap=None, times=None, fmap_segments=None, fmap_tol=1e-3, dcf=None, dcf_iters=30):
     """ksp: (1, readout, views, C, 1, ..., T), mps: (X, Y, Z, C, M), traj: (3, readout, views[, 1, ..., T]) in pixels -> image
     (X, Y, Z, 1, M, ..., T).  T > 1 time frames: the block-diagonal problem of the module docstring, one A_t per frame.
     M > 1 sets of maps: soft-SENSE, M images per frame (module docstring); not with tv_time, basis or toeplitz.
@@ -562,7 +609,9 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
     toeplitz: A^H A of every solver is `operators.ToeplitzNormal` (module docstring); A^H y still comes from the gridding operator
     fmap: a real (X, Y, Z) field map in Hz, with times: the sample times in seconds, (readout,) or (readout, views): the
     time-segmented off-resonance model of the module docstring with fmap_segments segments (None: the fewest that reach the model
-    error fmap_tol); one frame, one set of maps, no basis.  The unknown and the result are those of the plain run."""
+    error fmap_tol); one frame, one set of maps, no basis.  The unknown and the result are those of the plain run.
+    dcf: density-compensation weights with the axes of traj without the first, or 'auto' (Pipe-Menon, dcf_iters iterations, once per
+    distinct trajectory): the weighted data term of the module docstring; every solver runs unchanged on the weighted A and y."""
     from indigo_amd.transforms import FuseZpadFFT, Optimize, sense_recipe, soft_sense_tree
     from indigo_amd.transforms import reserve_for
     ksp = np.asarray(ksp, dtype=np.complex64)
@@ -650,13 +699,38 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
     recipe = sense_recipe(level)
     if fuse and level >= 3:
         recipe = recipe + [FuseZpadFFT]
+    rows = int(np.prod(ksp.shape[1:3]))                  # samples of one coil of one frame
+    dens = None
+    if dcf is not None and not (isinstance(dcf, str) and dcf == 'auto'):
+        dens = sample_density(dcf, traj.shape)
+        if dens.shape[1] not in (1, T_traj):
+            raise ValueError("--dcf: the weights have %d frames, the trajectory has %d" % (dens.shape[1], T_traj))
 
-    def frame_operators(trj3):
-        """A_t and A_t^H A_t + lamda I of one trajectory (in a temporal subspace A_t^H A_t alone: lamda acts on the coefficients)"""
+    def frame_density(trj3, t):
+        """the weights of the trajectory of frame t (of the trajectory's own frames), float64 (rows,), or None without --dcf"""
+        if dcf is None:
+            return None
+        if dens is not None:
+            return dens[:, t if dens.shape[1] > 1 else 0]
+        from indigo_amd.dcf import pipe_menon
+        return pipe_menon(B, trj3, mps.shape[:3], width=width, osf=osf, iters=dcf_iters).reshape(-1, order='F').astype(np.float64)
+
+    def weighted(A, wts):
+        """W^(1/2) A: the forward model of the density-compensated data term (one weight per sample, shared by the coils)"""
+        if wts is None:
+            return A
+        name = A._name
+        A = B.SampleWeights(np.sqrt(wts), rows, A.shape[0] // rows, name='sqrt dcf') * A
+        A._name = name
+        return A
+
+    def frame_operators(trj3, wts=None):
+        """A_t and A_t^H A_t + lamda I of one trajectory (in a temporal subspace A_t^H A_t alone: lamda acts on the coefficients);
+        wts: density-compensation weights of its samples, W^(1/2) A_t in place of A_t"""
         def nufft():
             return B.NUFFT(ksp_nc_dims[:3], mps.shape[:3], trj3, width=width, oversamp=(osf, osf, osf), dtype=ksp.dtype)
         if M > 1:
-            A = soft_sense_tree(B, nufft, mps.reshape(mps.shape[:3] + (C, M)), recipe)
+            A = weighted(soft_sense_tree(B, nufft, mps.reshape(mps.shape[:3] + (C, M)), recipe), wts)
             AHA = (A.H * A) + lamda * B.Eye(A.shape[1])
             AHA._name = 'SENSE'
             return A, AHA
@@ -665,39 +739,44 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
         S = B.VStack([B.Diag(mps[:, :, :, c].reshape(mps.shape[:3] + (1,))) for c in range(C)], name='maps')
         A = F * S
         A._name = 'SENSE1'
-        A = Optimize(recipe).visit(A)
+        A = weighted(Optimize(recipe).visit(A), wts)
         AHA = (A.H * A) + lamda * B.Eye(A.shape[1]) if phi is None else A.H * A
         AHA._name = 'SENSE'
         return A, AHA
 
     if T == 1:
         distinct, which = [traj.reshape(traj.shape[:3])], [0]
-        A, AHA = frame_operators(distinct[0])
+        density = [frame_density(distinct[0], 0)]
+        # (with a field map the weights go around the segments' combination, not into every segment's tree)
+        A, AHA = frame_operators(distinct[0], density[0] if seg is None else None)
+        wpanel = 0 if dcf is None else (A.shape[0] + 31) // 32 * 32          # the weighted product's extra k-space panel
         if seg is None:
-            reserve_for(AHA, 1, slack_products=6)
+            reserve_for(AHA, 1, slack_products=6, extra=wpanel)
         else:
             # the L segments are L frames on one trajectory: one tree under the BlockDiag.  Around it the product holds two panels
             # of the segments' images and two of their samples
             taus, table, period, _ = seg
-            N, L, rows = int(np.prod(mps.shape[:3])), taus.size, A.shape[0]
-            reserve_for(AHA, 1, slack_products=6, extra=2 * ((N * L + 31) // 32 * 32) + 2 * ((rows * L + 31) // 32 * 32))
+            N, L, krows = int(np.prod(mps.shape[:3])), taus.size, A.shape[0]
+            reserve_for(AHA, 1, slack_products=6, extra=2 * ((N * L + 31) // 32 * 32) + 2 * ((krows * L + 31) // 32 * 32) + wpanel)
             Phase = B.SegmentPhase(fmap.reshape(-1, order='F'), taus, N, name='segment phase')
-            A = B.SegmentCombine(table, period, rows, name='segment combine') * B.BlockDiag([A] * L, name='SENSE1 segments') * Phase
+            A = B.SegmentCombine(table, period, krows, name='segment combine') * B.BlockDiag([A] * L, name='SENSE1 segments') * Phase
             A._name = 'SENSE1 off-resonance'
+            A = weighted(A, density[0])
             AHA = (A.H * A) + lamda * B.Eye(N)
             AHA._name = 'SENSE off-resonance'
     else:
         # frames with equal trajectories share one tree: its matrices are built and uploaded once, and BlockDiag evaluates the
         # same child on each of those frames' rows in turn
         trjs = traj.reshape(traj.shape[:3] + (T_traj,))
-        distinct, trees, which = [], [], []
+        distinct, trees, which, density = [], [], [], []
         for t in range(T):
             trj3 = trjs[..., t if T_traj > 1 else 0]
             k = next((k for k, seen in enumerate(distinct) if np.array_equal(seen, trj3)), None)
             if k is None:
                 k = len(distinct)
                 distinct.append(trj3)
-                trees.append(frame_operators(trj3))
+                density.append(frame_density(trj3, t if T_traj > 1 else 0))
+                trees.append(frame_operators(trj3, density[-1]))
             which.append(k)
         log.info("frames %d, distinct trajectories %d", T, len(distinct))
         A = B.BlockDiag([trees[k][0] for k in which], name='SENSE1 frames')
@@ -705,8 +784,9 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
         # the children run one after the other on the same arena: the scratch of the most demanding one, once
         from indigo_amd.analyses import ScratchUsage
         worst = max((tree[1] for tree in trees), key=lambda node: ScratchUsage().measure(node, 1))
+        wpanel = 0 if dcf is None else (trees[0][0].shape[0] + 31) // 32 * 32   # the weighted product's extra k-space panel
         if phi is None:
-            reserve_for(worst, 1, slack_products=6)
+            reserve_for(worst, 1, slack_products=6, extra=wpanel)
         else:
             # x_t = sum_k Phi[t, k] alpha_k: the unknowns are the K coefficient images.  Below the frames' trees the three-factor
             # product holds two panels of all T frames: the synthesised frames and what the frames' operators make of them
@@ -716,10 +796,17 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
             A._name = 'SENSE1 subspace'
             AHA = Phi.H * AHA * Phi + lamda * B.Eye(N * K)
             AHA._name = 'SENSE subspace'
-            reserve_for(worst, 1, slack_products=6, extra=2 * ((N * T + 31) // 32 * 32))
+            reserve_for(worst, 1, slack_products=6, extra=2 * ((N * T + 31) // 32 * 32) + wpanel)
     log.info("tree:\n%s", AHA.dump())
     log.info('using %d MB of device memory', (AHA.memusage() + 4 * AHA.shape[1] * ksp.dtype.itemsize) / 1e6)
     y = np.asfortranarray(ksp.reshape((-1, 1), order='F'))
+    if dcf is not None:
+        # y <- sqrt(w) . y, frame by frame, before A^H y and ||y||^2: the data of the same weighted problem
+        sq = np.sqrt(np.stack([density[k] for k in which], axis=1)).astype(np.float32)
+        y = np.asfortranarray((y.reshape((rows, C, T), order='F') * sq[:, None, :]).astype(ksp.dtype).reshape((-1, 1), order='F'))
+        density = [np.square(np.sqrt(d).astype(np.float32).astype(np.float64)) for d in density]      # (what the operators apply)
+    else:
+        density = None
     AHy = A.H * y
     scale = abs(AHy).max()
     AHy /= scale
@@ -732,9 +819,9 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
         if seg is not None:
             Phase = B.SegmentPhase(fmap.reshape(-1, order='F'), seg[0], int(np.prod(mps.shape[:3])), name='segment phase')
             weights = np.tile(seg[1], (int(np.prod(ksp.shape[1:3])) // seg[2], 1))
-            AHA = toeplitz_normal(B, mps, distinct, which, None, lamda, width, osf, recipe=recipe, segments=(Phase, weights))
+            AHA = toeplitz_normal(B, mps, distinct, which, None, lamda, width, osf, recipe=recipe, segments=(Phase, weights), density=density)
         else:
-            AHA = toeplitz_normal(B, mps, distinct, which, phi, lamda, width, osf, recipe=recipe)
+            AHA = toeplitz_normal(B, mps, distinct, which, phi, lamda, width, osf, recipe=recipe, density=density)
         log.info("tree:\n%s", AHA.dump())
     if tv_time > 0 and T == 1:
         log.info("--tv-time %g has no effect on a scan with one time frame", tv_time)
@@ -785,6 +872,13 @@ def main(argv=None, backend=None):
         times = (args.te or 0.0) + args.dwell * np.arange(ksp.shape[1], dtype=np.float64)
     else:
         times = None
+    if args.dcf == 'auto':
+        dcf = 'auto'
+    elif args.dcf is not None or 'dcf' in extras:
+        dcf = (np.load(args.dcf) if args.dcf is not None else extras['dcf']).T
+        dcf = dcf[tuple(slice(0, min(n, c)) for n, c in zip(dcf.shape, crops[-2:-dcf.ndim - 2:-1]))]      # (its axes are the trajectory's from PHS1 on)
+    else:
+        dcf = None
     if args.cc is not None:
         from indigo_amd import cc
         ksp, mps = cc.compress(backend, ksp, mps, V=args.cc)[:2]
@@ -793,7 +887,7 @@ def main(argv=None, backend=None):
                       power_iters=args.power_iters, step=args.step, tv=args.tv, tv_sigma=args.tv_sigma, tv_time=args.tv_time,
                       llr=args.llr, llr_block=args.llr_block, llr_shifts=args.llr_shifts, llr_seed=args.llr_seed,
                       basis=basis, basis_rank=args.basis_rank, toeplitz=args.toeplitz,
-                      fmap=fmap, times=times, fmap_segments=args.fmap_segments, fmap_tol=args.fmap_tol)
+                      fmap=fmap, times=times, fmap_segments=args.fmap_segments, fmap_tol=args.fmap_tol, dcf=dcf, dcf_iters=args.dcf_iters)
     write(img.T)
     log.info("reconstruction complete")
     return img

@@ -54,7 +54,7 @@ def pack_planes(P, order='xyz'):
     return out
 
 
-def psf_kernel(B, dims, trajs, which, phi, width, osf, order='xyz', recipe=None, sample_weights=None):
+def psf_kernel(B, dims, trajs, which, phi, width, osf, order='xyz', recipe=None, sample_weights=None, density=None):
     """The kernel array of `ToeplitzNormal` for an image of `dims` voxels: host float32 (K^2, 8 prod dims), planes as in
     `pack_planes`, in the grid memory order `order`.
 
@@ -67,6 +67,9 @@ def psf_kernel(B, dims, trajs, which, phi, width, osf, order='xyz', recipe=None,
             time-segmented field-map model (indigo_amd.fmap): K = L, and pair (a, b) is the adjoint NUFFT of
             conj(w[:, a]) w[:, b] in place of W[a, b] times that of ones: L (L + 1) / 2 set-up transforms.  The kernel stays
             Hermitian at every grid point, psf_ba[d] = conj(psf_ab[-d]).  None: the planes are what they were without it.
+    density   optional: one real non-negative array per DISTINCT trajectory, a weight per sample (pics --dcf):
+            the kernel of A^H W A.  q_t becomes the adjoint NUFFT of w in place of that of ones, and with `sample_weights` the
+            pair products are multiplied by w.  None: the planes are what they were without it.
 
     q_t is computed once per distinct trajectory: B.NUFFT(..., N = 2 dims).H applied to ones.  The sample at image index j is the
     lag d = j - dims (the centred transform's origin), and psf[d] belongs at index d mod 2 dims: a circular shift by half the
@@ -96,6 +99,13 @@ def psf_kernel(B, dims, trajs, which, phi, width, osf, order='xyz', recipe=None,
     if not 1 <= K <= MAXK:
         raise ValueError("psf_kernel: %d coefficient images, at most %d are supported: the kernel array holds 4 K^2 bytes per grid point, "
                          "%.1f GB here (137 GB at K = 16 on a 512^3 grid)" % (K, MAXK, kernel_bytes(K, dims) / 1e9))
+    if density is not None:
+        if len(density) != len(trajs):
+            raise ValueError("psf_kernel: %d sets of sample weights for %d distinct trajectories" % (len(density), len(trajs)))
+        density = [np.asarray(w, dtype=np.float64).reshape(-1, order='F') for w in density]
+        for w, trj in zip(density, trajs):
+            if w.size != int(np.prod(np.asarray(trj).shape[1:])):
+                raise ValueError("psf_kernel: %d sample weights for a trajectory of %d samples" % (w.size, int(np.prod(np.asarray(trj).shape[1:]))))
     pairs = [(a, b) for a in range(K) for b in range(a, K)]
     vols = {}
     for d, trj in enumerate(trajs):
@@ -110,14 +120,16 @@ def psf_kernel(B, dims, trajs, which, phi, width, osf, order='xyz', recipe=None,
         reserve_for(F, 1, slack_products=4)
         if sample_weights is not None:
             for a, b in pairs:
-                w = (sample_weights[:, a].conj() * sample_weights[:, b]).astype(_C64).reshape((-1, 1))
+                w = sample_weights[:, a].conj() * sample_weights[:, b]
+                w = (w if density is None else w * density[d]).astype(_C64).reshape((-1, 1))
                 w = B.copy_array(np.asfortranarray(w), name='psf.weights')
                 vols[(a, b)] = B.zero_array((P, 1), _C64, name='psf.%d.%d' % (a, b))
                 F.H.eval(vols[(a, b)], w)
                 del w
             del F
             continue
-        ones = B.copy_array(np.ones((F.shape[0], 1), dtype=_C64, order='F'), name='psf.ones')
+        ones = np.ones((F.shape[0], 1), dtype=_C64, order='F') if density is None else np.asfortranarray(density[d].astype(_C64).reshape((-1, 1)))
+        ones = B.copy_array(ones, name='psf.ones')
         q = B.zero_array((P, 1), _C64, name='psf.q')
         F.H.eval(q, ones)
         del ones, F
