@@ -312,6 +312,31 @@ int  ig_psf_mix_c64(ig_ctx* ctx, int64_t n, int64_t nc, int64_t nk, const float*
  * beta != 0.                                                                                                                    */
 int  ig_coil_maps_c64(ig_ctx* ctx, int64_t n, int64_t nc, int64_t nm, const void* maps, int adjoint, const void* x,
                       float alpha_re, float alpha_im, float beta_re, float beta_im, void* y, int64_t ldi, int64_t sg, int64_t sc);
+/* The model kernels of NLINV, the joint estimation of the image and the coil sensitivities (indigo_amd.nlinv, operators.NlinvProduct,
+ * operators.SobolevCoils, Backend.nlinv_product, Backend.sobolev_weight).  No reference counterpart.
+ * ig_nlinv_product_c64: the derivative of the bilinear coil product rho * c_c at the point (rho, coils), and its adjoint
+ *     adjoint == 0:  y[i, c]     = beta*y[i, c]     + alpha * ( x[i, 0] * coils[i, c] + rho[i] * x[i, 1 + c] )
+ *     adjoint != 0:  y[i, 0]     = beta*y[i, 0]     + alpha * sum_c conj(coils[i, c]) * x[i, c]
+ *                    y[i, 1 + c] = beta*y[i, 1 + c] + alpha * conj(rho[i]) * x[i, c]
+ *   i < n voxels, c < nc coils.  rho is n dense elements; coils, x and y are device column-major panels (ldc, ldx, ldy >= n in
+ *   elements): coils has nc columns, forward x has 1 + nc and y nc, adjoint x has nc and y 1 + nc.  Rows between the columns are
+ *   never touched.  Pairs of voxels move with 16-byte accesses when n and the leading dimensions are even and all four pointers
+ *   16-byte aligned, single voxels with 8-byte accesses otherwise; both forms give the same bits.  The adjoint reads x once.
+ *   beta == 0: y is not read.  A y that overlaps x, rho or coils is IG_ERR_ARG, with nothing written.  n >= 1 and nc >= 1, else
+ *   IG_ERR_UNSUPPORTED.  One pass: 8 n (3 nc + 2) bytes either way, and 8 n (columns of y) more when beta != 0.
+ * ig_sobolev_weight_c64: y[k, j] = scale * w(k) * x[k, j] for the k < n0 n1 n2 points of an uncentred transform of an n0 x n1 x n2
+ *   volume (first axis fastest) and j < ncols columns, with
+ *     w(k) = (1 + a |kappa|^2)^(-b/2),   kappa_a = k'_a / n_a,   k'_a = k_a if 2 k_a <= n_a else k_a - n_a.
+ *   w is formed in double from the integer coordinates and rounded to float32 once, scale * w rounded to float32 once more, and the
+ *   product with x is one float32 product per component; w(k) and w(-k) are the same bits.  No weight array is stored.  x and y are
+ *   device column-major complex64 panels, ldx, ldy >= n0 n1 n2 in elements; rows between the columns are never touched.  b / 2 need
+ *   not be an integer.  y == x with ldy == ldx is the in-place form; any other overlap of y with x is IG_ERR_ARG, with nothing
+ *   written.  Every extent and ncols >= 1 and a >= 0, else IG_ERR_UNSUPPORTED.  One pass: 16 bytes per element.                  */
+int  ig_nlinv_product_c64(ig_ctx* ctx, int64_t n, int64_t nc, const void* rho, const void* coils, int64_t ldc, int adjoint,
+                          const void* x, int64_t ldx, float alpha_re, float alpha_im, float beta_re, float beta_im,
+                          void* y, int64_t ldy);
+int  ig_sobolev_weight_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t ncols, double a, double b, double scale,
+                           const void* x, int64_t ldx, void* y, int64_t ldy);
 /* ESPIRiT calibration at image resolution (indigo_amd.ecalib, Backend.place_wrapped, Backend.espirit_eig).  No
  * reference counterpart.
  * ig_place_wrapped_c64: vol is a device column-major panel of ncols volumes of n0 x n1 x n2 (first axis fastest), ld >= N = n0 n1 n2 in

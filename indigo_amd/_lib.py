@@ -95,6 +95,10 @@ PROTOTYPES = {
     "ig_psf_mix_c64":     (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64]),
     "ig_coil_maps_c64":   (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p,
                                    c_float, c_float, c_float, c_float, c_void_p, c_int64, c_int64, c_int64]),
+    "ig_nlinv_product_c64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64,
+                                     c_float, c_float, c_float, c_float, c_void_p, c_int64]),
+    "ig_sobolev_weight_c64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_double, c_double, c_double,
+                                      c_void_p, c_int64, c_void_p, c_int64]),
     "ig_place_wrapped_c64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64]),
     "ig_espirit_eig_c64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_float, c_void_p, c_int64, c_void_p, c_int64,
                                    c_void_p, c_int64]),

@@ -48,7 +48,7 @@ class Memusage(Visitor):
         if isinstance(node, op.ZpadFFTMaps) and id(node) not in self._seen:
             self._seen.add(id(node))
             self._base += node.maps_bytes()
-        if isinstance(node, (op.Product, op.UnscaledFFT, op.ZpadFFT, op.HeadRows)):
+        if isinstance(node, (op.Product, op.UnscaledFFT, op.ZpadFFT, op.HeadRows, op.SobolevCoils)):
             with self._push(self._live, self._round(node._mem_usage(self._ncols()))):
                 self._peak = max(self._peak, sum(self._live))
                 self.generic_visit(node)

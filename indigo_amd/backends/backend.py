@@ -512,6 +512,16 @@ class Backend(object):
         coil images stacked coil-major out (see operators.CoilMaps); .H is its adjoint"""
         return op.CoilMaps(self, maps, **kwargs)
 
+    def NlinvProduct(self, n, ncoils, **kwargs):
+        """the derivative of NLINV's bilinear coil product at a point set with `set_point`, shape (n C, n (1 + C)): (d rho | d c) in,
+        C coil images stacked coil-major out (see operators.NlinvProduct); .H is its adjoint"""
+        return op.NlinvProduct(self, n, ncoils, **kwargs)
+
+    def SobolevCoils(self, dims, ncoils, a, b, **kwargs):
+        """the coil weighting of NLINV on the unknown (rho, c^_1 ... c^_C) of a `dims` volume, shape (N (1 + C), N (1 + C)): rho
+        passes, every c^_c becomes the coil sensitivity W c^_c (see operators.SobolevCoils); .H is its adjoint"""
+        return op.SobolevCoils(self, dims, ncoils, a, b, **kwargs)
+
     def ZpadFFTMaps(self, grid_shape, box_shape, weights, maps, ncoils, **kwargs):
         """the fused ZpadFFT leaf with M images on its image side (see operators.ZpadFFTMaps)"""
         return op.ZpadFFTMaps(self, grid_shape, box_shape, weights, maps, ncoils, **kwargs)
@@ -886,6 +896,60 @@ class Backend(object):
             out[:, :C] = prod
             out = out.T if interleaved else out
         y.copy_from(np.asfortranarray(out.astype(_C64).reshape(y.shape, order='F')))
+
+    def nlinv_product(self, y, x, rho, coils, n, ncoils, adjoint=False, alpha=1, beta=0):
+        """y = beta*y + alpha * P x (adjoint: P^H x), the derivative of the bilinear coil product rho * c_c of NLINV at the point
+        (rho, coils) (indigo_amd.nlinv).  rho is a backend array of `n` values, coils the n x C panel of the coil
+        sensitivities (or the same as an (n C, 1) vector).  Forward, x is the n x (1 + C) panel (d rho | d c_1 ... d c_C), or the same
+        as an (n (1 + C), 1) vector, and y the n x C panel of coil images:  y[i, c] = x[i, 0] coils[i, c] + rho[i] x[i, 1 + c].
+        Adjoint, x holds the coil images and y the panel:  y[i, 0] = sum_c conj(coils[i, c]) x[i, c],
+        y[i, 1 + c] = conj(rho[i]) x[i, c].  beta == 0: y is not read; y must not overlap x, rho or coils.  Host form in float64
+        through to_host / copy_from; device backends override it."""
+        n, C = int(n), int(ncoils)
+        if C < 1 or n < 1:
+            raise RuntimeError("nlinv_product: %d voxels and %d coils, at least 1 each is supported" % (n, C))
+        cols_x, cols_y = (C, 1 + C) if adjoint else (1 + C, C)
+        assert rho.size == n and coils.size == n * C and x.size == n * cols_x and y.size == n * cols_y, (rho.shape, coils.shape, x.shape, y.shape, n, C)
+        r = rho.to_host().reshape(n).astype(np.complex128)
+        c = coils.to_host().reshape((n, C), order='F').astype(np.complex128)
+        v = x.to_host().reshape((n, cols_x), order='F').astype(np.complex128)
+        if adjoint:
+            out = np.concatenate([(np.conj(c) * v).sum(axis=1, keepdims=True), np.conj(r)[:, None] * v], axis=1)
+        else:
+            out = v[:, :1] * c + r[:, None] * v[:, 1:]
+        out = out * complex(alpha)
+        if beta != 0:
+            out = out + complex(beta) * y.to_host().reshape((n, cols_y), order='F').astype(np.complex128)
+        y.copy_from(np.asfortranarray(out.astype(_C64).reshape(y.shape, order='F')))
+
+    @staticmethod
+    def sobolev_weights(dims, a, b):
+        """w(k) = (1 + a |kappa|^2)^(-b/2) on the points of an uncentred transform of a `dims` volume, float64 dims-shaped:
+        kappa_a = k'_a / n_a with k'_a = k_a if 2 k_a <= n_a else k_a - n_a"""
+        r2 = 0.0
+        for ax, n in enumerate(dims):
+            k = np.arange(n, dtype=np.int64)
+            f = np.where(2 * k <= n, k, k - n).astype(np.float64) / float(n)
+            r2 = r2 + (f * f).reshape([-1 if j == ax else 1 for j in range(len(dims))])
+        return (1.0 + float(a) * r2) ** (-0.5 * float(b))
+
+    def sobolev_weight(self, y, x, dims, ncols, a, b, scale=1.0):
+        """y[k, j] = scale * w(k) * x[k, j] for the `ncols` columns of a panel of F-ordered `dims` k-space volumes (or the same as
+        one stacked column), w the smoothness weight of NLINV's coil penalty (`sobolev_weights`): w is rounded to float32 once and
+        scale * w once more, as the device kernel does.  y may be x (exactly in place); any other overlap is refused.  Host form
+        through to_host / copy_from; device backends override it."""
+        dims = tuple(int(n) for n in dims)
+        n, ncols = int(np.prod(dims)), int(ncols)
+        if len(dims) != 3 or min(dims) < 1 or ncols < 1 or not float(a) >= 0:
+            raise RuntimeError("sobolev_weight: dims %s, %d columns, a = %g: three positive lengths, at least one column and a >= 0" % (dims, ncols, a))
+        assert x.size == n * ncols and y.size == n * ncols, (x.shape, y.shape, dims, ncols)
+        w = self.sobolev_weights(dims, a, b).reshape(-1, order='F').astype(np.float32)
+        sw = (w.astype(np.float64) * float(scale)).astype(np.float32)
+        v = x.to_host().reshape((n, ncols), order='F')
+        out = np.empty((n, ncols), dtype=_C64, order='F')
+        out.real = sw[:, None] * v.real
+        out.imag = sw[:, None] * v.imag
+        y.copy_from(np.asfortranarray(out.reshape(y.shape, order='F')))
 
     def place_wrapped(self, vol, box, dims, box_dims):
         """Zero the columns of the panel `vol` (volumes of `dims`, F-order, one per column) and write column j of `box` (a dense array

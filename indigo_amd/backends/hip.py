@@ -962,6 +962,29 @@ class HipBackend(Backend):
         self._check(self._L.ig_coil_maps_c64(self._ctx, n, C, M, ctypes.c_void_p(maps._arr), int(bool(adjoint)), xp, ar, ai, br, bi,
                                              yp, ldi, sg, sc), "ig_coil_maps_c64")
 
+    def nlinv_product(self, y, x, rho, coils, n, ncoils, adjoint=False, alpha=1, beta=0):
+        """Backend.nlinv_product on the device (ig_nlinv_product_c64): the coils, x and y are the columns of panels with their
+        leading dimensions, or stacked in one column"""
+        assert x.dtype == _C64 and y.dtype == _C64 and rho.dtype == _C64 and coils.dtype == _C64, "only complex64 is supported"
+        n, C = int(n), int(ncoils)
+        assert rho.size == n and rho.contiguous, (rho.shape, n)
+        cols_x, cols_y = (C, 1 + C) if adjoint else (1 + C, C)
+        (cp, ldc), (xp, ldx), (yp, ldy) = self._frame_panel(coils, n, C), self._frame_panel(x, n, cols_x), self._frame_panel(y, n, cols_y)
+        ar, ai = _cplx(alpha)
+        br, bi = _cplx(beta)
+        self._check(self._L.ig_nlinv_product_c64(self._ctx, n, C, ctypes.c_void_p(rho._arr), cp, ldc, int(bool(adjoint)), xp, ldx,
+                                                 ar, ai, br, bi, yp, ldy), "ig_nlinv_product_c64")
+
+    def sobolev_weight(self, y, x, dims, ncols, a, b, scale=1.0):
+        """Backend.sobolev_weight on the device (ig_sobolev_weight_c64): the panels with their leading dimensions, or stacked in
+        one column; y may be x"""
+        assert x.dtype == _C64 and y.dtype == _C64, "only complex64 is supported"
+        n0, n1, n2 = (int(n) for n in dims)
+        n, ncols = n0 * n1 * n2, int(ncols)
+        (xp, ldx), (yp, ldy) = self._frame_panel(x, n, ncols), self._frame_panel(y, n, ncols)
+        self._check(self._L.ig_sobolev_weight_c64(self._ctx, n0, n1, n2, ncols, ctypes.c_double(float(a)), ctypes.c_double(float(b)),
+                                                  ctypes.c_double(float(scale)), xp, ldx, yp, ldy), "ig_sobolev_weight_c64")
+
     def place_wrapped(self, vol, box, dims, box_dims):
         """Backend.place_wrapped on the device (ig_place_wrapped_c64): the volumes are the columns of a panel with its leading
         dimension, or stacked in one column; the boxes are one dense array"""

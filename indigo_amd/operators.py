@@ -617,6 +617,108 @@ class CoilMaps(MatrixFreeOperator):
         return 0            # (no scratch: the maps themselves are counted with the matrices, analyses.Memusage)
 
 
+class NlinvProduct(MatrixFreeOperator):
+    """The derivative of NLINV's bilinear coil product rho * c_c at the point (rho, c), shape (n C, n (1 + C)).
+    The input is (d rho | d c_1 ... d c_C), block b in rows [bn, (b+1)n); the output is C coil images stacked coil-major,
+    coil image c = d rho * c_c + rho * d c_c, as `KronI(C, NUFFT)` consumes them.  .H is the adjoint:
+    d rho = sum_c conj(c_c) * z_c, d c_c = conj(rho) * z_c.  The point is two device arrays, rho (n) and c (n x C), handed over with
+    `set_point`: the Newton iteration swaps them between steps without rebuilding the tree, and the leaf keeps no copy."""
+
+    def __init__(self, backend, n, ncoils, **kwargs):
+        self._n, self._C = int(n), int(ncoils)
+        if self._n < 1 or self._C < 1:
+            raise ValueError("NlinvProduct: %d voxels and %d coils, at least 1 each is supported" % (self._n, self._C))
+        self._rho_d = self._coils_d = None
+        kwargs.setdefault('name', 'nlinv product')
+        super().__init__(backend, shape=(self._n * self._C, self._n * (1 + self._C)), **kwargs)
+
+    def set_point(self, rho_d, coils_d):
+        """the linearisation point: device arrays of n and n C elements, read at every evaluation until the next call"""
+        if rho_d.size != self._n or coils_d.size != self._n * self._C:
+            raise ValueError("NlinvProduct.set_point: rho %s and coils %s for %d voxels and %d coils" % (rho_d.shape, coils_d.shape, self._n, self._C))
+        self._rho_d, self._coils_d = rho_d, coils_d
+
+    def _eval(self, y, x, alpha=1, beta=0, forward=True, left=True):
+        if self._rho_d is None:
+            raise RuntimeError("NlinvProduct: no linearisation point, call set_point(rho, coils) first")
+        n, C = self._n, self._C
+        trace = getattr(self._backend, 'trace', None)
+        if trace is not None:
+            # a single pass: rho, the coils, x and y move once (8 B per voxel each); beta != 0 reads the output
+            trace.add('nlinv_product', nbytes=8 * n * (3 * C + 2) * x.shape[1] + (0 if beta == 0 else y.nbytes), nflops=16 * n * C * x.shape[1],
+                      shape=x.shape, forward=forward, name=self._name)
+        if x.shape[1] == 1:
+            return self._backend.nlinv_product(y, x, self._rho_d, self._coils_d, n, C, adjoint=not forward, alpha=alpha, beta=beta)
+        for j in range(x.shape[1]):             # the blocks become the columns of a panel inside: one product per column
+            self._backend.nlinv_product(y[:, j:j + 1], x[:, j:j + 1], self._rho_d, self._coils_d, n, C, adjoint=not forward, alpha=alpha, beta=beta)
+
+    def _mem_usage(self, ncols):
+        return 0            # (no scratch; the point belongs to the caller)
+
+
+class SobolevCoils(MatrixFreeOperator):
+    """The coil weighting of NLINV on the unknown u = (rho, c^_1 ... c^_C) of an F-ordered `dims` volume of N voxels, shape
+    (N (1 + C), N (1 + C)): rows [0, N) (rho) are copied through; every c^_c becomes the coil sensitivity
+
+        c_c = W c^_c = (1 / sqrt N) ifftn( w * c^_c ),      W^H z = w * fftn(z) / sqrt N,      w(k) = (1 + a |kappa|^2)^(-b/2)
+
+    with the backend's plain, uncentred, unnormalised transforms (Backend.sobolev_weights).  w is real and even, so
+    W commutes with shifts and no centring modulation is needed.  Forward is `sobolev_weight` (scale 1 / sqrt N) and `ifftn` in
+    place on the dims + (C,) view; the adjoint is `fftn`, then `sobolev_weight`.  With a real alpha and beta == 0 both run in the
+    output; otherwise the coil part goes through a scratch panel of N C elements and one axpby."""
+
+    def __init__(self, backend, dims, ncoils, a, b, **kwargs):
+        self._dims = tuple(int(n) for n in dims)
+        self._C = int(ncoils)
+        if len(self._dims) != 3 or min(self._dims) < 1 or self._C < 1:
+            raise ValueError("SobolevCoils: dims must be three positive lengths and coils at least 1, got %s and %s" % (dims, ncoils))
+        if not float(a) >= 0:
+            raise ValueError("SobolevCoils: a = %s, a non-negative value is supported" % (a,))
+        self._a, self._b = float(a), float(b)
+        self._N = int(np.prod(self._dims))
+        kwargs.setdefault('name', 'sobolev coils')
+        super().__init__(backend, shape=(self._N * (1 + self._C),) * 2, **kwargs)
+
+    def _coil_part(self, yc, xc, alpha, beta, forward):
+        """yc = beta*yc + alpha * (W or W^H) xc on contiguous vectors of N C elements"""
+        B, N, C = self._backend, self._N, self._C
+        vol = self._dims + (C,)
+        s = 1.0 / np.sqrt(float(N))
+
+        def run(dst, scale):
+            if forward:
+                B.sobolev_weight(dst, xc, self._dims, C, self._a, self._b, scale=scale)
+                B.ifftn(dst.reshape(vol), dst.reshape(vol))
+            else:
+                B.fftn(dst.reshape(vol), xc.reshape(vol))
+                B.sobolev_weight(dst, dst, self._dims, C, self._a, self._b, scale=scale)
+
+        if beta == 0 and np.imag(alpha) == 0:
+            run(yc, s * float(np.real(alpha)))
+        else:
+            with B.scratch(shape=(N * C, 1)) as tmp:
+                run(tmp, s)
+                B.axpby(beta, yc, alpha, tmp)
+
+    def _eval(self, y, x, alpha=1, beta=0, forward=True, left=True):
+        B, N, C = self._backend, self._N, self._C
+        trace = getattr(B, 'trace', None)
+        for j in range(x.shape[1]):
+            xj = x if x.shape[1] == 1 else x[:, j:j + 1]
+            yj = y if x.shape[1] == 1 else y[:, j:j + 1]
+            if trace is not None:
+                # the weight pass moves 16 B per element and the transform is booked as UnscaledFFT books it; rho is one axpby
+                trace.add('sobolev_weight', nbytes=16 * N * C, nflops=2 * N * C, shape=(N, C), forward=forward, name=self._name)
+                trace.add('fft', nbytes=4 * 8 * N * C, nflops=C * 5 * N * np.log2(max(N, 2)), shape=self._dims + (C,), forward=forward, name=self._name + '.F')
+                trace.add('axpby', nbytes=8 * N * (2 if beta == 0 else 3), name=self._name + '.rho')
+            B.axpby(beta, yj.dense_rows(0, N), alpha, xj.dense_rows(0, N))
+            self._coil_part(yj.dense_rows(N, N * (1 + C)), xj.dense_rows(N, N * (1 + C)), alpha, beta, forward)
+
+    def _mem_usage(self, ncols):
+        # the scratch panel of a complex alpha or a beta != 0, and what the in-place transform takes
+        return (self._N * self._C * 8 + 255) // 256 * 256 + self._backend._fft_workspace_size(self._dims + (self._C,))
+
+
 class AxisPermute(MatrixFreeOperator):
     """Relabelling of the axes of an F-ordered image volume of shape `dims`: output axis a is input axis perm[a], i.e.
     y = x.reshape(dims, order='F').transpose(perm).ravel(order='F');  the adjoint is the inverse permutation.  Pure data
