@@ -387,6 +387,27 @@ int  ig_coil_gram_c64(ig_ctx* ctx, int64_t n, int64_t nc, const void* x, int64_t
  * One pass: 8 nk + 12 bytes per voxel (the dictionary, 8 nk na bytes, stays in the L2), 8 nk na real flops per voxel.            */
 int  ig_dict_match_c64(ig_ctx* ctx, int64_t n, int64_t nk, int64_t na, const void* x, int64_t ldx, const void* d, int64_t ldd,
                        int32_t* idx, void* ip);
+/* Extended-phase-graph signal simulation: the signal curves of na atoms (T1, T2, B1) under one pulse program (indigo_amd.dictmatch
+ * --model fse / fisp, Backend.epg_signal).  No reference counterpart.  An atom's state is (F+_k, F-_k, Z_k),
+ * k < nstates, complex, with Z_0 = 1 and the rest 0 at the start.  Step s of the program is steps[4 s ... 4 s + 3] = (alpha, phi, a, b)
+ * (radians, seconds) and flags[s], bits 1 = SHIFT_A, 2 = SHIFT_B, 4 = RECORD, 8 = SPOIL, and runs in this order:
+ *     RF(B1 alpha, phi); relax(a); shift if SHIFT_A; record F+_0 if RECORD; relax(b); shift if SHIFT_B; F+ = F- = 0 if SPOIL
+ * RF, with theta = B1 alpha, c = cos^2(theta/2), s = sin^2(theta/2), e = exp(i phi), for every k:
+ *     F+' = c F+ + e^2 s F- - i e sin(theta) Z        F-' = conj(e)^2 s F+ + c F- + i conj(e) sin(theta) Z
+ *     Z'  = -(i/2) conj(e) sin(theta) F+ + (i/2) e sin(theta) F- + cos(theta) Z
+ * relax(d): F+ and F- times exp(-d/T2), Z times exp(-d/T1), then Z_0 gains -expm1(-d/T1).  shift: F+_k <- F+_(k-1) for k >= 1,
+ * F-_k <- F-_(k+1), F- at nstates - 1 <- 0, F+_0 <- conj(new F-_0); Z stays, and the F+ that leaves state nstates - 1 is lost (the
+ * truncation is part of the definition).  t1, t2 and b1 are device arrays of na float32, never written; steps and flags are HOST
+ * arrays, read before the call returns and copied to scratch that the context owns.  out is a device column-major complex64 panel,
+ * atom a in column a (ldo >= nrec in elements, nrec = the steps with RECORD, counted by the call): out[r + a ldo] is record r; rows
+ * below nrec are never touched.  The coefficients of a step are formed in double from the float32 parameters and rounded to
+ * float32 once; the state is float32 with fused multiply-adds in a fixed order, one wavefront per atom, no atomics: the bits of an
+ * atom's column do not depend on na or on the atom's place, and two calls give the same bits.  1 <= nsteps <= 65535,
+ * 1 <= nstates <= 256 and na >= 1, else IG_ERR_UNSUPPORTED; flags outside 0 ... 15, a value that is not finite, a negative
+ * duration, a program without RECORD, ldo < nrec or an out that overlaps t1, t2 or b1 is IG_ERR_ARG; nothing is written on refusal.
+ * About 74 nsteps min(nstates, shifts) real flops and 8 nrec + 12 bytes per atom.                                                */
+int  ig_epg_sim_c64(ig_ctx* ctx, int64_t na, int64_t nsteps, int64_t nstates, const float* t1, const float* t2, const float* b1,
+                    const double* steps, const int32_t* flags, void* out, int64_t ldo);
 /* Density compensation (indigo_amd.dcf, Backend.dcf_spread / dcf_gather_div / row_scale, pics --dcf).  No reference
  * counterpart.  The two halves of one Pipe-Menon iteration w <- w / (G G^H w) on ONE real column, G the gridding matrix of M samples
  * on the n0 x nm x ns grid in the separable form of ig_interp3_sep: `records` (device) built WITHOUT modulation and with scale 1, so

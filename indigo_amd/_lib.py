@@ -104,6 +104,7 @@ PROTOTYPES = {
                                    c_void_p, c_int64]),
     "ig_coil_gram_c64":   (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64]),
     "ig_dict_match_c64":  (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "ig_epg_sim_c64":     (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64]),
     "ig_dcf_spread_r32":  (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_double, c_int64,
                                    c_void_p, c_int64, c_int64, c_int64]),
     "ig_dcf_gather_div_r32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double,

@@ -1069,6 +1069,97 @@ class Backend(object):
             ip[i0:i0 + chunk] = P[np.arange(P.shape[0]), best]
         return idx, ip
 
+    EPG_SHIFT_A, EPG_SHIFT_B, EPG_RECORD, EPG_SPOIL = 1, 2, 4, 8
+    EPG_MAX_STATES, EPG_MAX_STEPS = 256, 65535
+
+    @classmethod
+    def epg_check(cls, params, steps, flags, nstates):
+        """-> (params float32 (N, 3), steps float64 (S, 4), flags int32 (S,), nstates, nrec) of `epg_signal`, checked: every refusal
+        is a ValueError that says what is wrong"""
+        p = np.asarray(params)
+        if p.ndim != 2 or p.shape[1] != 3 or p.shape[0] < 1:
+            raise ValueError("epg_signal: the parameters must be an (N, 3) array of (T1, T2, B1), got shape %s" % (p.shape,))
+        if np.iscomplexobj(p) or not np.isfinite(p).all():
+            raise ValueError("epg_signal: the parameters hold values that are not finite real numbers")
+        p = np.ascontiguousarray(p, dtype=np.float32)
+        if not (np.isfinite(p).all() and (p[:, :2] > 0).all()):
+            raise ValueError("epg_signal: T1 and T2 must be positive (and finite in float32)")
+        st = np.asarray(steps, dtype=np.float64)
+        fl = np.asarray(flags)
+        if st.ndim != 2 or st.shape[1] != 4 or not 1 <= st.shape[0] <= cls.EPG_MAX_STEPS:
+            raise ValueError("epg_signal: the program must be an (S, 4) array of (flip, phase, a, b) with 1 <= S <= %d, got shape %s"
+                             % (cls.EPG_MAX_STEPS, st.shape))
+        if fl.shape != (st.shape[0],) or fl.dtype.kind not in 'iu':
+            raise ValueError("epg_signal: the flags must be %d integers, one per step, got %s of shape %s" % (st.shape[0], fl.dtype, fl.shape))
+        if ((fl < 0) | (fl > 15)).any():
+            raise ValueError("epg_signal: flags must be in 0 ... 15 (1 SHIFT_A, 2 SHIFT_B, 4 RECORD, 8 SPOIL)")
+        if not np.isfinite(st).all():
+            raise ValueError("epg_signal: the program holds values that are not finite")
+        if (st[:, 2:] < 0).any():
+            raise ValueError("epg_signal: the program holds a negative duration")
+        fl = np.ascontiguousarray(fl, dtype=np.int32)
+        nrec = int(np.count_nonzero(fl & cls.EPG_RECORD))
+        if nrec < 1:
+            raise ValueError("epg_signal: the program records nothing (no step has the RECORD flag, 4)")
+        nstates = int(nstates)
+        if not 1 <= nstates <= cls.EPG_MAX_STATES:
+            raise ValueError("epg_signal: %d states, between 1 and %d are supported" % (nstates, cls.EPG_MAX_STATES))
+        return p, np.ascontiguousarray(st), fl, nstates, nrec
+
+    def epg_signal(self, params, steps, flags, nstates, chunk=1 << 16):
+        """Extended-phase-graph simulation (indigo_amd.dictmatch --model fse / fisp): the signal of N atoms under one
+        pulse program -> a host (N, nrec) complex64 array.  params is a host (N, 3) array of (T1, T2, B1), cast to float32; steps a
+        host (S, 4) float64 array of (flip, phase, a, b) per step, radians and seconds; flags S integers, bits 1 = SHIFT_A,
+        2 = SHIFT_B, 4 = RECORD, 8 = SPOIL.  An atom's state is (F+_k, F-_k, Z_k), k < nstates, Z_0 = 1 at the start; a step runs
+        RF(B1 flip, phase), relax(a), shift if SHIFT_A, record F+_0 if RECORD, relax(b), shift if SHIFT_B, F+ = F- = 0 if SPOIL, with
+        the operations of ig_epg_sim_c64 (include/indigo_hip.h).  Host form: float64 arithmetic on the float32-cast parameters,
+        vectorised over `chunk` atoms at a time; device backends override it."""
+        p, st, fl, K, nrec = self.epg_check(params, steps, flags, nstates)
+        N, chunk = p.shape[0], max(1, int(chunk))
+        out = np.empty((N, nrec), dtype=_C64)
+        for i0 in range(0, N, chunk):
+            q = p[i0:i0 + chunk].astype(np.float64)
+            T1, T2, B1 = q[:, 0:1], q[:, 1:2], q[:, 2:3]
+            n = q.shape[0]
+            Fp, Fm, Z = (np.zeros((n, K), dtype=np.complex128) for _ in range(3))
+            Z[:, 0] = 1.0
+
+            def relax(d):
+                if d == 0:
+                    return
+                E2 = np.exp(-d / T2)
+                Fp[...] *= E2
+                Fm[...] *= E2
+                Z[...] *= np.exp(-d / T1)
+                Z[:, 0] -= np.expm1(-d / T1[:, 0])
+
+            def shift():
+                Fp[:, 1:] = Fp[:, :-1].copy()
+                Fm[:, :-1] = Fm[:, 1:].copy()
+                Fm[:, -1] = 0
+                Fp[:, 0] = np.conj(Fm[:, 0])
+            r = 0
+            for (alpha, phi, a, b), f in zip(st, fl):
+                theta = B1 * alpha
+                e = np.exp(1j * phi)
+                c, s, sn = np.cos(theta / 2) ** 2, np.sin(theta / 2) ** 2, np.sin(theta)
+                Fp, Fm, Z = (c * Fp + (e * e) * s * Fm - 1j * e * sn * Z,
+                             np.conj(e * e) * s * Fp + c * Fm + 1j * np.conj(e) * sn * Z,
+                             -0.5j * np.conj(e) * sn * Fp + 0.5j * e * sn * Fm + np.cos(theta) * Z)
+                relax(a)
+                if f & self.EPG_SHIFT_A:
+                    shift()
+                if f & self.EPG_RECORD:
+                    out[i0:i0 + n, r] = Fp[:, 0]
+                    r += 1
+                relax(b)
+                if f & self.EPG_SHIFT_B:
+                    shift()
+                if f & self.EPG_SPOIL:
+                    Fp[...] = 0
+                    Fm[...] = 0
+        return out
+
     @staticmethod
     def _dcf_taps(rec, tw, dims):
         """(cells, taps) of the separable records `rec` (rows of at least 3 tw + 2 words), each (rows, tw^3): the grid cell of every

@@ -1038,6 +1038,23 @@ class HipBackend(Backend):
                                               ctypes.c_void_p(idx._arr), ctypes.c_void_p(ip._arr)), "ig_dict_match_c64")
         return idx.to_host().ravel(), ip.to_host().ravel()
 
+    def epg_signal(self, params, steps, flags, nstates, chunk=1 << 16):
+        """Backend.epg_signal on the device (ig_epg_sim_c64): the parameters go up and the signals come down `chunk` atoms at a
+        time; the program is handed over by host pointer with every call"""
+        p, st, fl, K, nrec = self.epg_check(params, steps, flags, nstates)
+        N, chunk = p.shape[0], max(1, int(chunk))
+        out = np.empty((N, nrec), dtype=_C64)
+        for i0 in range(0, N, chunk):
+            n = min(chunk, N - i0)
+            cols = [self.copy_array(np.asfortranarray(p[i0:i0 + n, c:c + 1]), name='epg.param') for c in range(3)]
+            sig = self.empty_array((nrec, n), _C64, name='epg.signal')
+            self._check(self._L.ig_epg_sim_c64(self._ctx, n, st.shape[0], K, *(ctypes.c_void_p(c._arr) for c in cols),
+                                               ctypes.c_void_p(st.ctypes.data), ctypes.c_void_p(fl.ctypes.data),
+                                               ctypes.c_void_p(sig._arr), sig._leading_dim), "ig_epg_sim_c64")
+            out[i0:i0 + n] = sig.to_host().T
+            del cols, sig
+        return out
+
     def _dcf_args(self, what, w, records, sep, tiles):
         """(M, tw, records, stride, order) of the Pipe-Menon kernels' common arguments, checked"""
         f32, u32 = np.dtype('float32'), np.dtype('uint32')

@@ -29,6 +29,8 @@ struct ig_ctx {
     double*      d_scalars   = nullptr;   // IG_NUM_SCALARS device-resident doubles for solver scalars (ig_scalars)
     void*        d_xpack     = nullptr;   // SpMM repacked-panel scratch (grown on demand)
     size_t       xpack_bytes = 0;
+    void*        d_epg       = nullptr;   // the uploaded pulse program of ig_epg_sim_c64 (grown on demand)
+    size_t       epg_bytes   = 0;
     int32_t*     d_worklist  = nullptr;   // SpMM deferred-row lists + counters (allocated on first use)
     size_t       worklist_bytes = 0, partials_bytes = 0, scalars_bytes = 0;   // what was really allocated (ig_library_bytes)
     // plan options (ig_set_option): which transform kernels a NEW plan may use.  0 = all; 1 = no register-resident A x B passes

@@ -95,6 +95,7 @@ void ig_destroy(ig_ctx* ctx) {
     if (ctx->d_scalars) (void)hipFree(ctx->d_scalars);
     if (ctx->d_worklist) (void)hipFree(ctx->d_worklist);
     if (ctx->d_xpack) (void)hipFree(ctx->d_xpack);
+    if (ctx->d_epg) (void)hipFree(ctx->d_epg);
     if (ctx->h_result) (void)hipHostFree(ctx->h_result);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -206,9 +207,9 @@ int ig_set_option(ig_ctx* ctx, const char* name, int64_t value) {
 int ig_library_bytes(ig_ctx* ctx, size_t* bytes) {
     IG_REQUIRE(ctx, ctx && bytes, "ig_library_bytes: bad arguments");
     // device memory the library itself holds for this context: the repacked-panel buffer of the SpMM kernels (grown on
-    // demand), the deferred-row lists, the reduction scratch and the solver scalars
+    // demand), the pulse program of the EPG simulation, the deferred-row lists, the reduction scratch and the solver scalars
     // (the byte counts are recorded where the buffers are allocated)
-    *bytes = ctx->xpack_bytes + (ctx->d_worklist ? ctx->worklist_bytes : 0) + (ctx->d_partials ? ctx->partials_bytes : 0) +
+    *bytes = ctx->xpack_bytes + ctx->epg_bytes + (ctx->d_worklist ? ctx->worklist_bytes : 0) + (ctx->d_partials ? ctx->partials_bytes : 0) +
              (ctx->d_scalars ? ctx->scalars_bytes : 0);
     return IG_OK;
 }

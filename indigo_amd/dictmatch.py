@@ -4,6 +4,10 @@
 
     python -m indigo_amd.dictmatch basis --model t2 --te S --echoes T --t2 lo:hi:N (--rank K | --energy E) out
     python -m indigo_amd.dictmatch basis --model ir --ti FILE.npy --t1 lo:hi:N (--rank K | --energy E) out
+    python -m indigo_amd.dictmatch basis --model fse --te S --echoes T (--flip DEG | --flips FILE.npy) --t2 lo:hi:N [--t1 lo:hi:N]
+                                         [--b1 lo:hi:N] [--states K] (--rank K | --energy E) out
+    python -m indigo_amd.dictmatch basis --model fisp --flips FILE.npy --tr VALUE|FILE.npy --te S [--phases FILE.npy] [--ti S]
+                                         --t1 lo:hi:N --t2 lo:hi:N [--b1 lo:hi:N] [--states K] (--rank K | --energy E) out
     python -m indigo_amd.dictmatch basis --atoms FILE.npy --params FILE.npy (--rank K | --energy E) out
     python -m indigo_amd.dictmatch fit --atoms A.npy --params P.npy --basis phi.npy [--basis-rank K] [--mask-rel 0.02] [--chunk N] rec.npy
 
@@ -12,7 +16,19 @@
 atoms, K given by `--rank` or as the smallest K whose singular values hold the fraction `--energy` of their squared sum.  Two models
 need no input: multi-echo spin echo, s_t = exp(-t TE / T2) at the echoes t = 1 ... T, and inversion recovery,
 s = 1 - 2 exp(-TI / T1) at the inversion times of `--ti`; both on a log-spaced grid lo:hi:N of their parameter (seconds, as TE and
-TI).  `--atoms` with `--params` takes any dictionary simulated elsewhere (an EPG or Bloch simulation, several parameters per atom).
+TI).  `--atoms` with `--params` takes any dictionary simulated elsewhere (a Bloch simulation, several parameters per atom).
+
+Two more models run on the extended-phase-graph simulator, `Backend.epg_signal` (ig_epg_sim_c64 on the device, one wavefront per atom;
+DESIGN.md §3.19; tests/epg64.py restates it in float64).  An atom is (T1, T2, B1), B1 scaling every flip angle; `params` is (N, 3) in
+that order, the atoms ordered with T1 slowest and B1 fastest, T1 and T2 on log-spaced grids and B1 on a linear one (`--t1` and `--b1`
+default to the single value 1.0 where they are optional).  `--model fse` is a CPMG echo train with imperfect and variable refocusing:
+an excitation (90 degrees, phase 90 degrees) and T refocusing pulses of `--flip` degrees, or of the T angles in `--flips`, `--te`
+apart, one record per echo; `--states` defaults to min(T + 1, 256), which truncates nothing up to T = 255.  `--model fisp` is an
+unbalanced steady-state train as MR fingerprinting runs it: an optional inversion (180 degrees, `--ti` seconds, spoiled), then per
+pulse the flip angle of `--flips` (degrees) and the phase of `--phases` (degrees, default 0), a record `--te` after the pulse and one
+dephasing shift per repetition of `--tr` seconds (a value, or a file of T values); atoms with T2 > T1 are dropped; `--states` defaults
+to 32.  `program_fse` and `program_fisp` return the `(steps, flags)` that `epg_signal` takes: with them any program can be run from
+Python.  The simulation runs on `--backend` / `--device`, `--chunk` atoms at a time.
 
 `fit` reads `rec.npy`, the coefficient images exactly as `pics --basis` saves them (stored reversed, K on the COEFF axis), and writes,
 stored reversed like every array of a scan,
@@ -30,11 +46,11 @@ matched atom is the smallest a that attains max_a |d_a^H c|^2, and rho = d_a^H c
 Where the work runs.  The matching step is a (voxels x K)(K x N) complex product followed by an arg-max over N,
 `Backend.dict_match` (ig_dict_match_c64 on the device: float32-input MFMA fused with a running maximum per voxel, the scores are
 never stored).  The dictionary is uploaded once; the voxels of a host array go through the device in chunks of at most `--chunk`.
-The simulation, the SVD and the compression are host work in float64.  `fit_frames` serves a reconstruction of T frames made without
+The closed-form models, the SVD and the compression are host work in float64.  `fit_frames` serves a reconstruction of T frames made without
 `--basis`: it projects the frames with `Backend.frame_basis(adjoint=True)` and matches the same way.
 
-Left out: interpolation between the atoms of the grid, a search restricted by a per-voxel B1 map, EPG simulation,
-dictionaries beyond the L2.
+Left out: interpolation between the atoms of the grid, a search restricted by a per-voxel B1 map, dictionaries
+beyond the L2.
 
 The backend is the MI355X one (`hip`); `main(argv, backend=...)` lets the CPU test-suite drive the same code with the numpy oracle.
 """
@@ -50,13 +66,14 @@ _C64 = np.dtype('complex64')
 
 MAX_COEFFS = 32         # Backend.dict_match (and Backend.frame_basis) keep at most 32 coefficients per voxel
 CHUNK = 1 << 21         # voxels of a host array on the device at a time
+EPG_CHUNK = 1 << 16     # atoms of an EPG simulation on the device at a time
 COEFF = 6               # the COEFF axis of a `pics --basis` result
 
 
 # ---- the dictionary and its basis -------------------------------------------------------------------------------------------------
 
-def grid(spec):
-    """'lo:hi:N' -> N log-spaced values from lo to hi (float64)"""
+def grid(spec, log=True):
+    """'lo:hi:N' -> N log-spaced (or, log=False, evenly spaced) values from lo to hi (float64)"""
     try:
         lo, hi, N = spec.split(":")
         lo, hi, N = float(lo), float(hi), int(N)
@@ -64,7 +81,9 @@ def grid(spec):
         raise ValueError("dictmatch: a parameter grid is lo:hi:N, got %r" % (spec,))
     if not (0 < lo <= hi and N >= 1):
         raise ValueError("dictmatch: a parameter grid lo:hi:N needs 0 < lo <= hi and N >= 1, got %r" % (spec,))
-    return np.geomspace(lo, hi, N) if N > 1 else np.array([lo])
+    if N == 1:
+        return np.array([lo])
+    return np.geomspace(lo, hi, N) if log else np.linspace(lo, hi, N)
 
 
 def atoms_t2(te, echoes, t2):
@@ -83,6 +102,77 @@ def atoms_ir(ti, t1):
         raise ValueError("dictmatch: --model ir needs at least one inversion time, none of them negative")
     t1 = np.asarray(t1, dtype=np.float64).ravel()
     return 1.0 - 2.0 * np.exp(-ti[None, :] / t1[:, None]), t1[:, None].copy()
+
+
+# ---- extended-phase-graph programs (Backend.epg_signal) ---------------------------------------------------------------------------
+
+SHIFT_A, SHIFT_B, RECORD, SPOIL = 1, 2, 4, 8        # the flag bits of a step
+MAX_STATES = 256
+
+
+def _program(rows):
+    steps = np.array([r[:4] for r in rows], dtype=np.float64).reshape(-1, 4)
+    return steps, np.array([r[4] for r in rows], dtype=np.int32)
+
+
+def program_fse(te, flips):
+    """CPMG echo train -> (steps (T + 1, 4) float64, flags (T + 1,) int32) for `Backend.epg_signal`: an excitation (pi/2, phase pi/2)
+    followed by te/2 and a shift, then for each of the T refocusing angles `flips` (radians): the pulse (phase 0), te/2, a shift, the
+    record of the echo, te/2, a shift.  T records."""
+    flips = np.asarray(flips, dtype=np.float64).ravel()
+    if not (np.isfinite(te) and te > 0):
+        raise ValueError("dictmatch: an fse program needs an echo spacing --te > 0, got %r" % (te,))
+    if flips.size < 1 or not np.isfinite(flips).all():
+        raise ValueError("dictmatch: an fse program needs at least one refocusing flip angle, all of them finite")
+    rows = [(np.pi / 2, np.pi / 2, te / 2, 0.0, SHIFT_A)]
+    rows += [(a, 0.0, te / 2, te / 2, SHIFT_A | RECORD | SHIFT_B) for a in flips]
+    return _program(rows)
+
+
+def program_fisp(flips, tr, te, phases=None, ti=None):
+    """Unbalanced steady-state (fingerprinting) train -> (steps, flags) for `Backend.epg_signal`: if `ti` is given an inversion
+    (pi, phase 0), ti and a spoiler; then for pulse t of the T `flips` (radians; `phases` radians, default 0): the pulse, te, the
+    record, tr[t] - te, a shift.  `tr` is one value or T values.  T records."""
+    flips = np.asarray(flips, dtype=np.float64).ravel()
+    T = flips.size
+    if T < 1 or not np.isfinite(flips).all():
+        raise ValueError("dictmatch: a fisp program needs at least one flip angle, all of them finite")
+    tr = np.asarray(tr, dtype=np.float64).ravel()
+    if tr.size == 1:
+        tr = np.full(T, tr[0])
+    if tr.size != T:
+        raise ValueError("dictmatch: %d flip angles and %d repetition times: --tr is one value or one per flip angle" % (T, tr.size))
+    phases = np.zeros(T) if phases is None else np.asarray(phases, dtype=np.float64).ravel()
+    if phases.size != T or not np.isfinite(phases).all():
+        raise ValueError("dictmatch: %d flip angles and %d phases: --phases holds one finite value per flip angle" % (T, phases.size))
+    if not (np.isfinite(te) and te >= 0):
+        raise ValueError("dictmatch: a fisp program needs an echo time --te >= 0, got %r" % (te,))
+    if not np.isfinite(tr).all() or (tr < te).any():
+        t = int(np.argmax(~(tr >= te)))
+        raise ValueError("dictmatch: repetition time %g of pulse %d is below the echo time %g" % (tr[t], t, te))
+    rows = []
+    if ti is not None:
+        if not (np.isfinite(ti) and ti >= 0):
+            raise ValueError("dictmatch: the inversion time --ti must be >= 0, got %r" % (ti,))
+        rows.append((np.pi, 0.0, float(ti), 0.0, SPOIL))
+    rows += [(flips[t], phases[t], te, tr[t] - te, RECORD | SHIFT_B) for t in range(T)]
+    return _program(rows)
+
+
+def check_states(nstates):
+    if not 1 <= nstates <= MAX_STATES:
+        raise ValueError("dictmatch: --states %d, between 1 and %d are supported" % (nstates, MAX_STATES))
+    return int(nstates)
+
+
+def atom_grid(t1, t2, b1, drop_t2_above_t1=False):
+    """-> (N, 3) float64 rows (T1, T2, B1) of the product grid, T1 slowest and B1 fastest; optionally without the rows with T2 > T1"""
+    g = np.stack([a.ravel() for a in np.meshgrid(t1, t2, b1, indexing='ij')], axis=1)
+    if drop_t2_above_t1:
+        g = g[g[:, 1] <= g[:, 0]]
+        if g.shape[0] < 1:
+            raise ValueError("dictmatch: every atom of the grid has T2 > T1, nothing is left to simulate")
+    return np.ascontiguousarray(g)
 
 
 def check_dictionary(atoms, params):
@@ -221,12 +311,24 @@ def parse(argv):
                                  "pics --basis from simulated signal curves, `fit` turns the coefficient images into quantitative maps.")
     sub = ap.add_subparsers(dest='command', required=True)
     b = sub.add_parser('basis', help='simulate a dictionary and write <out>.atoms.npy, <out>.params.npy and <out>.phi.npy')
-    b.add_argument('--model', choices=['t2', 'ir'], default=None, help='t2: multi-echo spin echo; ir: inversion recovery')
-    b.add_argument('--te', type=float, default=None, help='echo spacing in seconds (--model t2)')
-    b.add_argument('--echoes', type=int, default=None, help='number of echoes T (--model t2)')
-    b.add_argument('--t2', default=None, help='lo:hi:N, a log-spaced grid of T2 values in seconds (--model t2)')
-    b.add_argument('--ti', default=None, help='a .npy file with the T inversion times in seconds (--model ir)')
-    b.add_argument('--t1', default=None, help='lo:hi:N, a log-spaced grid of T1 values in seconds (--model ir)')
+    b.add_argument('--model', choices=['t2', 'ir', 'fse', 'fisp'], default=None,
+                   help='t2: multi-echo spin echo; ir: inversion recovery; fse: CPMG echo train (EPG); fisp: unbalanced steady-state train (EPG)')
+    b.add_argument('--te', type=float, default=None, help='echo spacing (--model t2, fse) or echo time (--model fisp) in seconds')
+    b.add_argument('--echoes', type=int, default=None, help='number of echoes T (--model t2, fse)')
+    b.add_argument('--t2', default=None, help='lo:hi:N, a log-spaced grid of T2 values in seconds (--model t2, fse, fisp)')
+    b.add_argument('--ti', default=None, help='a .npy file with the T inversion times in seconds (--model ir); the inversion time in '
+                   'seconds (--model fisp, optional)')
+    b.add_argument('--t1', default=None, help='lo:hi:N, a log-spaced grid of T1 values in seconds (--model ir, fisp; fse: default 1.0)')
+    b.add_argument('--b1', default=None, help='lo:hi:N, an evenly spaced grid of B1 scales of the flip angles (--model fse, fisp; default 1.0)')
+    b.add_argument('--flip', type=float, default=None, help='the refocusing flip angle in degrees (--model fse)')
+    b.add_argument('--flips', default=None, help='a .npy file with the T flip angles in degrees (--model fse, fisp)')
+    b.add_argument('--phases', default=None, help='a .npy file with the T pulse phases in degrees (--model fisp, default 0)')
+    b.add_argument('--tr', default=None, help='the repetition time in seconds, or a .npy file with T of them (--model fisp)')
+    b.add_argument('--states', type=int, default=None, help='configuration states kept, 1 ... 256 (--model fse: default min(T + 1, 256); '
+                   'fisp: default 32)')
+    b.add_argument('--chunk', type=int, default=EPG_CHUNK, help='atoms simulated on the device at a time (--model fse, fisp)')
+    b.add_argument('--backend', type=str, default='hip', choices=['hip'], help='where --model fse and fisp are simulated')
+    b.add_argument('--device', type=int, default=0)
     b.add_argument('--atoms', default=None, help='a .npy file with an (N, T) dictionary simulated elsewhere (with --params)')
     b.add_argument('--params', default=None, help='a .npy file with the (N, P) parameters of --atoms')
     how = b.add_mutually_exclusive_group(required=True)
@@ -246,13 +348,51 @@ def parse(argv):
     for p in (b, f):
         p.add_argument('--debug', type=int, default=logging.INFO, help='logging level')
     args = ap.parse_args(argv)
-    if args.command == 'fit' and args.chunk < 1:
+    if args.chunk < 1:
         ap.error("--chunk must be at least 1")
     return args
 
 
-def simulate(args):
-    """the (atoms, params) of a `basis` run: one of the two models, or the files of --atoms and --params"""
+def _degrees(path, what):
+    a = np.asarray(np.load(path), dtype=np.float64).ravel()
+    if a.size < 1 or not np.isfinite(a).all():
+        raise ValueError("dictmatch basis: %s holds no values, or values that are not finite" % what)
+    return np.deg2rad(a)
+
+
+def epg_program(args):
+    """-> (steps, flags, nstates, (N, 3) params) of `basis --model fse | fisp`"""
+    b1 = grid(args.b1, log=False) if args.b1 is not None else np.array([1.0])
+    if args.model == 'fse':
+        if args.te is None or args.echoes is None or args.t2 is None or (args.flip is None) == (args.flips is None):
+            raise ValueError("dictmatch basis: --model fse needs --te, --echoes, --t2 and either --flip or --flips")
+        if args.echoes < 1:
+            raise ValueError("dictmatch basis: --model fse needs --echoes >= 1")
+        flips = np.full(args.echoes, np.deg2rad(args.flip)) if args.flip is not None else _degrees(args.flips, "--flips")
+        if flips.size != args.echoes:
+            raise ValueError("dictmatch basis: --flips holds %d angles for --echoes %d" % (flips.size, args.echoes))
+        steps, flags = program_fse(args.te, flips)
+        nstates = check_states(args.states if args.states is not None else min(args.echoes + 1, MAX_STATES))
+        t1 = grid(args.t1) if args.t1 is not None else np.array([1.0])
+        return steps, flags, nstates, atom_grid(t1, grid(args.t2), b1)
+    if args.flips is None or args.tr is None or args.te is None or args.t1 is None or args.t2 is None:
+        raise ValueError("dictmatch basis: --model fisp needs --flips, --tr, --te, --t1 and --t2")
+    try:
+        tr = np.array([float(args.tr)])
+    except ValueError:
+        tr = np.asarray(np.load(args.tr), dtype=np.float64).ravel()
+    try:
+        ti = None if args.ti is None else float(args.ti)
+    except ValueError:
+        raise ValueError("dictmatch basis: --model fisp takes the inversion time --ti as a value in seconds, got %r" % (args.ti,))
+    steps, flags = program_fisp(_degrees(args.flips, "--flips"), tr, args.te,
+                                phases=None if args.phases is None else _degrees(args.phases, "--phases"), ti=ti)
+    nstates = check_states(args.states if args.states is not None else 32)
+    return steps, flags, nstates, atom_grid(grid(args.t1), grid(args.t2), b1, drop_t2_above_t1=True)
+
+
+def simulate(args, backend=None):
+    """the (atoms, params) of a `basis` run: one of the four models, or the files of --atoms and --params"""
     given = (args.model is not None) + (args.atoms is not None)
     if given != 1:
         raise ValueError("dictmatch basis: give either --model or --atoms with --params")
@@ -264,6 +404,13 @@ def simulate(args):
         if args.te is None or args.echoes is None or args.t2 is None:
             raise ValueError("dictmatch basis: --model t2 needs --te, --echoes and --t2")
         return atoms_t2(args.te, args.echoes, grid(args.t2))
+    if args.model in ('fse', 'fisp'):
+        steps, flags, nstates, params = epg_program(args)
+        if backend is None:
+            from indigo_amd.backends import get_backend
+            backend = get_backend(args.backend, device_id=args.device)
+        log.info("simulating %d atoms, %d steps, %d states on %s", params.shape[0], steps.shape[0], nstates, type(backend).__name__)
+        return check_dictionary(backend.epg_signal(params, steps, flags, nstates, chunk=args.chunk), params)
     if args.ti is None or args.t1 is None:
         raise ValueError("dictmatch basis: --model ir needs --ti and --t1")
     return atoms_ir(np.load(args.ti), grid(args.t1))
@@ -273,7 +420,7 @@ def main(argv=None, backend=None):
     args = parse(sys.argv[1:] if argv is None else argv)
     logging.basicConfig(level=args.debug)
     if args.command == 'basis':
-        atoms, params = simulate(args)
+        atoms, params = simulate(args, backend)
         phi, sv = basis_of(atoms, rank=args.rank, energy=args.energy)
         K = phi.shape[1]
         log.info("%d atoms of %d time points, %d basis vectors hold %.8f of the energy", atoms.shape[0], atoms.shape[1], K,
