@@ -35,6 +35,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
+#include <type_traits>
 
 namespace {
 
@@ -1075,8 +1076,24 @@ namespace {
 //     lane (r, coil) fetches X[sample of round r, coil] (one load: the 64/TPR panel rows of the super-trip), the samples
 //     coming from `round_rows` a super-trip earlier.  A super-trip in flight costs 6 registers, so entries are requested
 //     three super-trips (192 entries) ahead and panel rows two;
-//   * accumulating: in round r lane (t, coil) takes entry r*TPR + t and X[round r, coil] from the loading lanes with
-//     ds_bpermute and adds conj(v) * x into the image with a plain read-add-write.
+//   * accumulating: in round r lane (t, coil) takes entry r*TPR + t and X[round r, coil] from the loading lanes and adds
+//     conj(v) * x into the image with a plain read-add-write.
+// How the values get from the loading to the accumulating lane depends on NC:
+//   * NC = 8 (every instantiation, real and complex weights): in registers, on the vector pipe.  Which lane needs what is fixed, so
+//     the entries are LOADED permuted -- lane 16 R + j fetches entry (j >> 1) * 8 + 2 R + (j & 1) of the super-trip (still one load per
+//     lane over the same 64 consecutive entries) -- and then sit in the 16-lane row R that accumulates them: round r takes row-lanes
+//     2 r and 2 r + 1 with two DPP row broadcasts per word (row_newbcast under bank masks 0x3 / 0xc: lanes 0..7 of a row are t = 2 R,
+//     lanes 8..15 t = 2 R + 1).  The panel rows: row p of the wave holds X[rounds 2 p and 2 p + 1, coil]; one v_permlane32_swap and two
+//     v_permlane16_swap per component and super-trip copy each row into all four (four registers per component for the length of the
+//     super-trip), and per round one row_ror:8 under a bank mask copies the round's half-row into the other half.  A DPP control is an
+//     immediate: the rounds run in PAIRS, the loop over the four pairs stays rolled and rotates the next pair into place (row_ror:12 on
+//     the entry words, register renaming on the panel rows), so the flush is inlined twice per super-trip.  All of it executes with the
+//     full execution mask (a DPP read of an inactive lane delivers nothing): before the divergence on the padding cell.  Per round
+//     6 (complex weights: 8) DPP moves and about 3 plain moves replace 4 (5) ds_bpermute and their address arithmetic; the LDS pipe
+//     is left with the image's ds_read_b64 / ds_write_b64.  48..60 VGPRs (at most four more than before), 8 waves per SIMD, no scratch
+//     (profiles/bricks_handoff_resources.txt); 0.65 -> 0.48 ms on the headline (profiles/bricks_handoff_ab.txt).
+//   * NC = 4 (16 entries x 4 columns per round, four rounds per super-trip): ds_bpermute as before -- four (five) per round of 64
+//     multiply-adds is half the hand-off cost per entry of the 8-column kernel; a register form for it was neither built nor measured.
 // An earlier form gave every lane of a round its own copy of the entry and the panel value straight from memory: eight
 // times the load instructions (address-unit time) and registers, which capped the prefetch depth at 64 entries.
 // At a brick boundary (wave-uniform test, once per round -- a brick holds at least one round) the image is stored and
@@ -1112,6 +1129,11 @@ k_grid_bricks(const BrickTask* __restrict__ tasks, int ntasks, const BrickRef* _
     const int BM = 1 << bm_log2, nseg = NSEG ? (PAIR ? 2 * NSEG : NSEG) : 1 << seg_log2, ncell = 16 << (bm_log2 + bs_log2);
     float2* __restrict__ acc = acc_all + (size_t)wv * ncell * NC;
     const int coil = lane % NC, tsub = lane / NC, xround = (lane / NC) % RS;
+    // REGS (8 columns): entries and panel rows reach the accumulating lane through DPP moves and the half/row swaps, not ds_bpermute.
+    // Lane 16 R + j then loads entry (j >> 1) * 8 + 2 R + (j & 1) of the super-trip: row-lanes 2 r and 2 r + 1 of row R hold the two
+    // entries (t = 2 R, 2 R + 1) that row accumulates in round r.
+    constexpr bool REGS = NC == 8;
+    const int eslot = REGS ? ((lane & 15) >> 1) * 8 + 2 * (lane >> 4) + (lane & 1) : lane;
     const rsrc_t r_en = REALW ? make_rsrc(reinterpret_cast<const float2*>(entries) + tk.lo) : make_rsrc(entries + tk.lo);
     const rsrc_t r_rr = make_rsrc(round_rows + tk.lo / TPR), r_x = make_rsrc(Xp);
 
@@ -1124,7 +1146,7 @@ k_grid_bricks(const BrickTask* __restrict__ tasks, int ntasks, const BrickRef* _
         s.rid = (uint32_t)buf_ld_i32(r_rr, q < nround ? (unsigned)q * 4u : IG_OOB);
     };
     auto request_entries = [&](Set& s, int st) {         // (past the end of the task: nothing is fetched)
-        const int32_t idx = st * 64 + lane;
+        const int32_t idx = st * 64 + eslot;
         if (REALW) {
             const float2 t = buf_ld<false>(r_en, idx < nent ? (unsigned)idx * 8u : IG_OOB, 0);
             s.en.x = __float_as_uint(t.x); s.en.y = __float_as_uint(t.y); s.en.z = 0u;
@@ -1235,16 +1257,7 @@ k_grid_bricks(const BrickTask* __restrict__ tasks, int ntasks, const BrickRef* _
         request_rows(rows_ahead, st + 2);
         request_entries(entries_ahead, st + 3);
         request_samples(next, st + 5);                                    // (the samples it held have served their purpose)
-        for (int r = 0; r < RS; ++r) {
-            const int32_t start = st * 64 + r * TPR;                      // wave-uniform; tasks begin and end on multiples of TPR
-            if (start >= nent) break;
-            if (start >= cur_end) flush();                                // (every brick of the table holds at least one round)
-            const int from_e = (r * TPR + tsub) * 4, from_x = (r * NC + coil) * 4;
-            const uint32_t cell = (uint32_t)__builtin_amdgcn_ds_bpermute(from_e, (int)e_cell);
-            const float vr = __int_as_float(__builtin_amdgcn_ds_bpermute(from_e, (int)e_re));
-            const float vi = REALW ? 0.f : __int_as_float(__builtin_amdgcn_ds_bpermute(from_e, (int)e_im));
-            const float xr = __int_as_float(__builtin_amdgcn_ds_bpermute(from_x, __float_as_int(x_re)));
-            const float xi = __int_as_float(__builtin_amdgcn_ds_bpermute(from_x, __float_as_int(x_im)));
+        auto accumulate = [&](uint32_t cell, float vr, float vi, float xr, float xi) {
             if (cell != 0xffffffffu) {
                 float2* a = acc + (int)cell * NC + coil;
                 float2 v = *a;                                            // plain read-add-write: the entries of a round belong to
@@ -1256,6 +1269,64 @@ k_grid_bricks(const BrickTask* __restrict__ tasks, int ntasks, const BrickRef* _
                     v.y += fmaf(vr, xi, -vi * xr);
                 }
                 *a = v;
+            }
+        };
+        if constexpr (REGS) {
+            // Panel rows: row p of the wave holds X[rounds 2 p and 2 p + 1, coil].  One half swap and two row swaps per component make
+            // every row of u?[p] that row.  (All of this, and the DPP moves below, with the full execution mask: before the divergence
+            // on the cell, and the tests on `start` are wave-uniform.)
+            int ur[4], ui[4];
+            {
+                const unsigned wr = __float_as_uint(x_re), wi = __float_as_uint(x_im);
+                const auto hr = __builtin_amdgcn_permlane32_swap(wr, wr, false, false);       // rows {0, 1, 0, 1} and {2, 3, 2, 3}
+                const auto hi = __builtin_amdgcn_permlane32_swap(wi, wi, false, false);
+                const auto r01 = __builtin_amdgcn_permlane16_swap(hr[0], hr[0], false, false), r23 = __builtin_amdgcn_permlane16_swap(hr[1], hr[1], false, false);
+                const auto i01 = __builtin_amdgcn_permlane16_swap(hi[0], hi[0], false, false), i23 = __builtin_amdgcn_permlane16_swap(hi[1], hi[1], false, false);
+                ur[0] = (int)r01[0]; ur[1] = (int)r01[1]; ur[2] = (int)r23[0]; ur[3] = (int)r23[1];
+                ui[0] = (int)i01[0]; ui[1] = (int)i01[1]; ui[2] = (int)i23[0]; ui[3] = (int)i23[1];
+            }
+            int ec = (int)e_cell, ew = (int)e_re, ez = (int)e_im;
+            // The DPP controls are immediates, so the rounds go in pairs: the loop over the pairs stays rolled (the flush is inlined twice
+            // per super-trip, not eight times) and moves the next pair into place at its end -- the entries by a row rotation that
+            // brings row-lanes 4..7 to 0..3, the panel rows by renaming.
+            auto round = [&](int start, auto half) -> bool {
+                constexpr int H = decltype(half)::value;
+                if (start >= nent) return false;                          // wave-uniform; tasks begin and end on multiples of TPR
+                if (start >= cur_end) flush();                            // (every brick of the table holds at least one round)
+                // lanes 0..7 of a row take the entry in row-lane 2 H, lanes 8..15 the one in row-lane 2 H + 1
+                constexpr int LO = 0x150 + 2 * H, HI = 0x151 + 2 * H;     // row_newbcast:n
+                const uint32_t cell = (uint32_t)__builtin_amdgcn_update_dpp(__builtin_amdgcn_mov_dpp(ec, LO, 0xf, 0x3, false), ec, HI, 0xf, 0xc, false);
+                const float vr = __int_as_float(__builtin_amdgcn_update_dpp(__builtin_amdgcn_mov_dpp(ew, LO, 0xf, 0x3, false), ew, HI, 0xf, 0xc, false));
+                const float vi = REALW ? 0.f : __int_as_float(__builtin_amdgcn_update_dpp(__builtin_amdgcn_mov_dpp(ez, LO, 0xf, 0x3, false), ez, HI, 0xf, 0xc, false));
+                // round 2 p + H sits in half-row H of u?[0]: the other half-row takes it rotated by eight lanes (row_ror:8)
+                const float xr = __int_as_float(__builtin_amdgcn_update_dpp(ur[0], ur[0], 0x128, 0xf, H ? 0x3 : 0xc, false));
+                const float xi = __int_as_float(__builtin_amdgcn_update_dpp(ui[0], ui[0], 0x128, 0xf, H ? 0x3 : 0xc, false));
+                accumulate(cell, vr, vi, xr, xi);
+                return true;
+            };
+#pragma unroll 1
+            for (int p = 0; p < RS / 2; ++p) {
+                const int32_t start = st * 64 + p * 2 * TPR;
+                if (!round(start, std::integral_constant<int, 0>())) break;
+                if (!round(start + TPR, std::integral_constant<int, 1>())) break;
+                ec = __builtin_amdgcn_mov_dpp(ec, 0x12c, 0xf, 0xf, false);                   // row_ror:12: lane i takes lane i + 4
+                ew = __builtin_amdgcn_mov_dpp(ew, 0x12c, 0xf, 0xf, false);
+                if (!REALW) ez = __builtin_amdgcn_mov_dpp(ez, 0x12c, 0xf, 0xf, false);
+                ur[0] = ur[1]; ur[1] = ur[2]; ur[2] = ur[3];
+                ui[0] = ui[1]; ui[1] = ui[2]; ui[2] = ui[3];
+            }
+        } else {
+            for (int r = 0; r < RS; ++r) {
+                const int32_t start = st * 64 + r * TPR;                  // wave-uniform; tasks begin and end on multiples of TPR
+                if (start >= nent) break;
+                if (start >= cur_end) flush();                            // (every brick of the table holds at least one round)
+                const int from_e = (r * TPR + tsub) * 4, from_x = (r * NC + coil) * 4;
+                const uint32_t cell = (uint32_t)__builtin_amdgcn_ds_bpermute(from_e, (int)e_cell);
+                const float vr = __int_as_float(__builtin_amdgcn_ds_bpermute(from_e, (int)e_re));
+                const float vi = REALW ? 0.f : __int_as_float(__builtin_amdgcn_ds_bpermute(from_e, (int)e_im));
+                const float xr = __int_as_float(__builtin_amdgcn_ds_bpermute(from_x, __float_as_int(x_re)));
+                const float xi = __int_as_float(__builtin_amdgcn_ds_bpermute(from_x, __float_as_int(x_im)));
+                accumulate(cell, vr, vi, xr, xi);
             }
         }
     };
