@@ -329,6 +329,10 @@ class Backend(object):
         self._scratch = self.empty_array((max(int(nelems), 1),), _C64, name='scratch')
         self._scratch_pos = 0
 
+    def release_scratch(self):
+        """Drop the arena: `scratch()` allocates dynamically until the next `reserve_scratch`."""
+        self._scratch = None
+
     @contextmanager
     def scratch(self, shape=None, nbytes=None):
         assert not (shape is not None and nbytes is not None), \

@@ -97,7 +97,7 @@ def check_size(kdims, C):
 def calib_from_noncart(B, ksp, traj, r, K3C, osf=640 / 480, width=3):
     """ksp: (1, readout, views, C[, 1, ..., T]), traj: (3, readout, views[, 1, ..., T]) in pixels -> the (r, r, r, C) complex128
     calibration block from the samples with max_a |k_a| <= r / 2 of all frames (step 1 of the module docstring)"""
-    from indigo_amd.pics import power_iteration
+    from indigo_amd.solvers import power_iteration
     from indigo_amd.transforms import reserve_for
     ksp = np.asarray(ksp)
     traj = np.asarray(traj, dtype=np.float64)
@@ -135,7 +135,7 @@ def calib_from_noncart(B, ksp, traj, r, K3C, osf=640 / 480, width=3):
     log.info("calibration images: largest eigenvalue of F^H F %.6e, lamda %.6e, %d CG iterations", L, lamda, CG_ITERS)
     x = np.zeros((r ** 3 * C, 1), dtype=_C64, order='F')
     B.cg(AHA, b, x, lamda=lamda, maxiter=CG_ITERS)
-    B._scratch = None
+    B.release_scratch()
     img = x.reshape((r, r, r, C), order='F').astype(np.complex128)
     ax = (0, 1, 2)
     return np.fft.fftshift(np.fft.fftn(np.fft.ifftshift(img, axes=ax), axes=ax), axes=ax) / np.sqrt(float(r) ** 3)

@@ -79,7 +79,7 @@ def nlinv(B, ksp, traj, dims, iters=8, cg_iters=10, alpha=1.0, redu=2.0, a=220.0
     the steps of the module docstring; history holds one {'alpha', 'cg_iters', 'residual'} per Newton step, residual being
     ||y - F(u_{n+1})|| / ||y|| after the step.  state: a dict that receives the iterate the results are made of: 'rho' (N,) and 'coils'
     (N, C) complex64 as the device holds them, 'L' and 's'."""
-    from indigo_amd.pics import power_iteration
+    from indigo_amd.solvers import power_iteration
     from indigo_amd.transforms import reserve_for
     ksp = np.asarray(ksp)
     traj = np.array(traj, dtype=np.float64)
@@ -151,7 +151,7 @@ def nlinv(B, ksp, traj, dims, iters=8, cg_iters=10, alpha=1.0, redu=2.0, a=220.0
 
     point = cu.to_host().reshape((N, 1 + C), order='F')
     del DFHDF, DF, A, F1HF1
-    B._scratch = None
+    B.release_scratch()
     if state is not None:
         state.update(rho=point[:, 0].copy(), coils=point[:, 1:].copy(), L=L, s=s)
     rho, c = point[:, 0].astype(np.complex128), point[:, 1:].astype(np.complex128)

@@ -157,13 +157,15 @@ The backend is the MI355X one (`hip`); there is no CPU fallback in the product. 
 CPU test-suite drive the same code with the numpy oracle backend.
 """
 import argparse
+import collections
+import inspect
 import logging
 import os
 import sys
 
 import numpy as np
 
-from indigo_amd.util import rand64c
+from indigo_amd.solvers import fista_solve, llr_term, power_iteration, tv_solve      # noqa: F401  (power_iteration: for those who took it from here)
 
 log = logging.getLogger("pics")
 
@@ -367,231 +369,264 @@ def toeplitz_normal(B, mps, distinct, which, phi, lamda, width, osf, recipe=None
     N = int(np.prod(dims))
     maps = mps.reshape(dims + (-1,))
     order = ToeplitzNormal.memory_order(B, dims)
+
+    def normal(trajs, frames, basis, K, name, tree, dens, wrap=lambda T: T, weights=None):
+        """lamda I + wrap(the `ToeplitzNormal` of K images `name` with the point-spread functions of `trajs`), named `tree`"""
+        kern = psf_kernel(B, dims, trajs, frames, basis, width, osf, order=order, recipe=recipe, sample_weights=weights, density=dens)
+        # (lamda I + T, not T + lamda I: a Sum evaluates its right child first, with the caller's beta, so T runs with beta = 0)
+        AHA = lamda * B.Eye(N * (1 if basis is None else K)) + wrap(B.ToeplitzNormal(dims, maps, kern, K, order=order, name=name))
+        AHA._name = tree
+        return AHA
     if segments is not None:
         Phase, weights = segments
-        L = weights.shape[1]
-        kern = psf_kernel(B, dims, distinct, which, None, width, osf, order=order, recipe=recipe, sample_weights=weights, density=density)
-        AHA = lamda * B.Eye(N) + Phase.H * B.ToeplitzNormal(dims, maps, kern, L, order=order, name='toeplitz segments') * Phase
-        AHA._name = 'SENSE off-resonance (Toeplitz)'
-        reserve_for(AHA, 1, slack_products=6)
-        return AHA
-    if phi is not None:
-        K = phi.shape[1]
-        kern = psf_kernel(B, dims, distinct, which, phi, width, osf, order=order, recipe=recipe, density=density)
-        # (lamda I + T, not T + lamda I: a Sum evaluates its right child first, with the caller's beta, so T runs with beta = 0)
-        AHA = lamda * B.Eye(N * K) + B.ToeplitzNormal(dims, maps, kern, K, order=order, name='toeplitz subspace')
-        AHA._name = 'SENSE subspace (Toeplitz)'
-        reserve_for(AHA, 1, slack_products=6)
-        return AHA
-    ops = []
-    for k, trj3 in enumerate(distinct):
-        kern = psf_kernel(B, dims, [trj3], [0], None, width, osf, order=order, recipe=recipe, density=None if density is None else [density[k]])
-        ops.append(lamda * B.Eye(N) + B.ToeplitzNormal(dims, maps, kern, 1, order=order, name='toeplitz'))
-        ops[-1]._name = 'SENSE (Toeplitz)'
-    AHA = ops[0] if len(which) == 1 else B.BlockDiag([ops[k] for k in which], name='SENSE frames (Toeplitz)')
+        ops = [normal(distinct, which, None, weights.shape[1], 'toeplitz segments', 'SENSE off-resonance (Toeplitz)', density,
+                      lambda T: Phase.H * T * Phase, weights)]
+    elif phi is not None:
+        ops = [normal(distinct, which, phi, phi.shape[1], 'toeplitz subspace', 'SENSE subspace (Toeplitz)', density)]
+    else:
+        ops = [normal([trj3], [0], None, 1, 'toeplitz', 'SENSE (Toeplitz)', None if density is None else [density[k]])
+               for k, trj3 in enumerate(distinct)]
+    frames = segments is None and phi is None and len(which) > 1
+    AHA = B.BlockDiag([ops[k] for k in which], name='SENSE frames (Toeplitz)') if frames else ops[0]
     # (the children run one after the other on the same arena, and all have the same size)
     reserve_for(ops[0], 1, slack_products=6)
     return AHA
 
 
-def power_iteration(B, AHA, iters, seed=0):
-    """largest eigenvalue of the Hermitian positive semi-definite AHA: `iters` power iterations from a seeded random start,
-    the estimate ||AHA v|| for the last unit vector v"""
-    n = AHA.shape[1]
-    v = B.copy_array(rand64c(n, 1, seed=seed), name='power.v')
-    w = B.zero_array((n, 1), np.dtype('complex64'), name='power.w')
-    B.scale(v, 1.0 / np.sqrt(B.norm2(v)))
-    lam = 0.0
-    for _ in range(int(iters)):
-        AHA.eval(w, v)
-        lam = float(np.sqrt(B.norm2(w)))
-        if lam == 0:
-            break
-        B.axpby(0, v, 1.0 / lam, w)
-    return lam
+# ---- the stages of `reconstruct` --------------------------------------------------------------------------------------------------------
+
+# the sizes of a scan: the image `dims` of N voxels, C coils, M sets of maps, T time frames of which the trajectory has T_traj (1 or T),
+# `samples` = (1, readout, views) with `rows` = readout views samples per coil and frame, and `img_dims`, the shape of the result
+Geometry = collections.namedtuple('Geometry', 'dims N C M T T_traj samples rows img_dims')
 
 
-def wavelet_prox(B, W, dims, l1):
-    """proxg(v, alpha) of l1 ||W v||_1 (W's coarse band excluded): v <- W^H soft_{alpha l1}(W v), in place (W is unitary); a v
-    of several frames stacked is the panel of its frames, and W and the threshold act on every column"""
-    n = int(np.prod(dims))
-
-    def proxg(v, alpha):
-        W.eval(v, v)
-        B.soft_threshold(v.reshape((n, -1)), alpha * l1, dims, W.coarse)
-        W.H.eval(v, v)
-    return proxg
-
-
-def wavelet_l1(coef, dims, coarse):
-    """sum |coef| outside the coarse box of every frame, in complex128; coef: the host (N T, 1) wavelet coefficients"""
-    coef = coef.reshape(tuple(dims) + (-1,), order='F')
-    inside = np.zeros(tuple(dims), dtype=bool)
-    inside[tuple(slice(0, c) for c in coarse)] = True
-    return float(np.abs(coef[~inside].astype(np.complex128)).sum())
-
-
-class ProxTerm:
-    """a non-smooth term g of the objective, as the solvers take it: proxg(v, alpha) replaces v by prox_{alpha g}(v) in place,
-    value(x) is g(x) as a float, text describes it in the log"""
-
-    def __init__(self, proxg, value, text):
-        self.proxg, self.value, self.text = proxg, value, text
+def geometry(ksp, mps, traj):
+    """the `Geometry` of ksp (1, readout, views, C, 1, ..., T), mps (X, Y, Z, C, M) and traj (3, readout, views[, 1, ..., T])"""
+    M = mps.shape[dim.MAPS] if mps.ndim > dim.MAPS else 1          # sets of coil maps: M > 1 is soft-SENSE, M images per frame
+    if ksp.ndim > dim.MAPS and ksp.shape[dim.MAPS] != 1:
+        raise ValueError("data has a MAPS axis of length %d: only the maps carry several sets, the k-space is one measurement "
+                         "(MAPS must be 1 in data)" % ksp.shape[dim.MAPS])
+    img_dims = mps.shape[:3] + (1,) + ksp.shape[4:]
+    if M > 1:
+        img_dims = img_dims + (1,) * (dim.MAPS + 1 - len(img_dims))
+        img_dims = img_dims[:dim.MAPS] + (M,) + img_dims[dim.MAPS + 1:]
+    log.info('img %s %s', img_dims, ksp.dtype)
+    log.info('mps %s, ksp %s, trj %s, sets of maps %d', mps.shape, ksp.shape, traj.shape, M)
+    T = ksp.shape[dim.TIME] if ksp.ndim > dim.TIME else 1
+    T_traj = traj.shape[dim.TIME] if traj.ndim > dim.TIME else 1
+    assert M == 1 or int(np.prod(mps.shape[dim.MAPS + 1:])) == 1, "Of the maps only COIL and MAPS may be longer than 1."
+    assert mps.ndim <= dim.TIME or mps.shape[dim.TIME] == 1, "The maps carry no TIME axis: one set for all frames."
+    assert T_traj in (1, T), "traj has %d time frames, data has %d" % (T_traj, T)
+    assert int(np.prod(ksp.shape[4:])) == T and int(np.prod(traj.shape[3:])) == T_traj, "Only COIL and TIME may be longer than 1."
+    return Geometry(tuple(mps.shape[:3]), int(np.prod(mps.shape[:3])), ksp.shape[dim.COIL], M, T, T_traj, tuple(ksp.shape[:3]),
+                    int(np.prod(ksp.shape[1:3])), img_dims)
 
 
-def wavelet_term(B, dims, l1, wavelet='db2', levels=3):
-    """l1 ||W x||_1 (W: operators.Wavelet on every frame, coarse band not penalised)"""
-    W = B.Wavelet(dims, wavelet=wavelet, levels=levels)
-    work = {}
-
-    def value(x):
-        if 'w' not in work:
-            work['w'] = B.zero_array(x.shape, np.dtype('complex64'), name='objective.w')
-        W.eval(work['w'], x)
-        return l1 * wavelet_l1(work['w'].to_host(), dims, W.coarse)
-    return ProxTerm(wavelet_prox(B, W, dims, l1), value,
-                    "%s wavelet, %d levels, coarse box %s of %s, l1 %g" % (wavelet, levels, W.coarse, tuple(dims), l1))
-
-
-def llr_term(B, dims, frames, lam, block=8, shifts=False, seed=0):
-    """lam sum_b ||M_b(x)||_*: the locally low-rank penalty on `frames` time frames with blocks of `block` voxels a side (clamped
-    to `dims`).  proxg is Backend.llr_threshold with the threshold alpha lam, at shift (0, 0, 0) or, with `shifts`, at a shift
-    drawn before every call, uniformly in [0, side) per axis from numpy.random.default_rng(seed) on the host.  value is that of
-    shift 0."""
-    dims = tuple(int(n) for n in dims)
-    T = int(frames)
-    sides = tuple(min(int(block), n) for n in dims)
-    rng = np.random.default_rng(seed) if shifts else None
-
-    def proxg(v, alpha):
-        shift = tuple(int(rng.integers(0, b)) for b in sides) if shifts else (0, 0, 0)
-        B.llr_threshold(v, alpha * lam, dims, T, sides, shift)
-
-    def value(x):
-        return lam * B.llr_norm(x, dims, T, sides)
-    return ProxTerm(proxg, value, "locally low rank, blocks %s of %s, %d frames, lambda %g, %s" % (
-        sides, dims, T, lam, "a random shift per prox call (seed %d)" % seed if shifts else "shift (0, 0, 0)"))
-
-
-def fista_solve(B, AHA, AHy, dims, iters, l1, wavelet='db2', levels=3, power_iters=15, step=None, ynorm2=0.0, term=None):
-    """min_x 1/2 x^H AHA x - Re(x^H AHy) + ynorm2 / 2 + g(x) by Backend.fista from x = 0, g = l1 ||W x||_1 (W's coarse band
-    excluded; `wavelet_term`) or the `term` given in its place (`llr_term`);
-    with AHA = A^H A + lamda I and AHy = A^H y that is 1/2 ||A x - y||^2 + lamda/2 ||x||^2 + g(x) for ynorm2 = ||y||^2.
-    AHA of NT columns is T frames of the `dims` volume stacked: W and the threshold then act on every frame.
-    Returns the image as a host (N, 1) array and the objectives logged: [(iteration, value)], every 10 iterations and the last."""
-    c64 = np.dtype('complex64')
-    if term is None:
-        term = wavelet_term(B, dims, l1, wavelet, levels)
-    if step is None:
-        lam = power_iteration(B, AHA, power_iters)
-        step = 0.9 / lam
-        log.info("fista: largest eigenvalue of A^H A + lamda I %.6e (%d power iterations), step %.6e", lam, power_iters, step)
-    else:
-        log.info("fista: step %.6e (given)", step)
-    log.info("fista: %s", term.text)
-    n = AHA.shape[1]
-    b = B.copy_array(AHy, name='AHy')
-
-    def gradf(g, z):
-        AHA.eval(g, z)
-        B.axpby(1, g, -1, b)
-
-    objectives = []
-    work = {}
-
-    def objective(k, x):
-        if not (k % 10 == 9 or k == iters - 1) or not log.isEnabledFor(logging.INFO):
-            return
-        if not work:
-            work['q'] = B.zero_array((n, 1), c64, name='objective.q')
-        q = work['q']
-        AHA.eval(q, x)
-        val = 0.5 * B.dot(x, q) - B.dot(x, b) + 0.5 * ynorm2 + term.value(x)
-        objectives.append((k + 1, val))
-        log.info("fista iter %d, objective %.9e", k + 1, val)
-
-    x = np.zeros((n, 1), dtype=c64, order='F')
-    B.fista(gradf, term.proxg, step, x, maxiter=iters, callback=objective)
-    return x, objectives
+def check_options(g, tv_time=0.0, l1=0.0, llr=0.0, basis=None, basis_rank=None, toeplitz=False):
+    """refuses the options that the scan `g` or one another rule out (a field map and density weights are checked where they are read:
+    `field_map_segments`, `sample_density`) -> the checked T x K basis of `subspace_basis`, or None"""
+    M, T = g.M, g.T
+    if M > 1:
+        # soft-SENSE follow-ups (DESIGN.md §7): the unknown is ordered maps inside frames, which is not what these three take
+        if tv_time > 0:
+            raise ValueError("--tv-time cannot be combined with M = %d sets of maps: GradientT differences neighbouring columns of the "
+                             "unknown, which are then the images of one frame's sets, not neighbouring frames" % M)
+        if basis is not None:
+            raise ValueError("--basis cannot be combined with M = %d sets of maps: FrameBasis mixes the columns of the unknown as "
+                             "frames, and they are then the images of the sets inside every frame" % M)
+        if toeplitz:
+            raise ValueError("--toeplitz cannot be combined with M = %d sets of maps: ToeplitzNormal takes one set" % M)
+        if M > 4:
+            raise ValueError("%d sets of maps, at most 4 are supported (Backend.coil_maps)" % M)
+        if llr > 0 and M * T > 32:
+            raise ValueError("--llr: M * T = %d x %d = %d columns, at most 32 are supported (Backend.llr_threshold)" % (M, T, M * T))
+    # (the two that `parse` refuses already)
+    assert basis is None or not tv_time > 0, "--tv-time cannot be combined with --basis: differences between coefficients are not differences in time"
+    assert not (llr > 0 and l1 > 0), "--llr and --l1 cannot be combined: two non-smooth terms in one prox slot are not a prox"
+    if basis is None:
+        return None
+    phi = subspace_basis(basis, T, basis_rank)
+    K = phi.shape[1]
+    gram = phi.astype(np.complex128)
+    log.info("basis: %d frames, %d coefficients, ||Phi^H Phi - I|| %.3e", T, K, np.linalg.norm(gram.conj().T @ gram - np.eye(K)))
+    if toeplitz and K > 8:
+        raise ValueError("--toeplitz: %d coefficients, at most 8 are supported: the kernel array holds 4 K^2 bytes per point of the "
+                         "doubled grid, %.1f GB here (--basis-rank keeps the first K columns)" % (K, 32e-9 * K * K * g.N))
+    return phi
 
 
-def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', levels=3, power_iters=15, step=None, ynorm2=0.0,
-             frames=1, mu_t=0.0, term=None):
-    """min_x 1/2 x^H AHA x - Re(x^H AHy) + ynorm2 / 2 + mu sum_i ||(D x)_i||_2 [+ l1 ||W x||_1] by Backend.primal_dual from x = 0,
-    u = 0: with AHA = A^H A + lamda I and AHy = A^H y that is 1/2 ||A x - y||^2 + lamda/2 ||x||^2 + mu TV(x) [+ l1 ||W x||_1] for
-    ynorm2 = ||y||^2.  D is operators.Gradient; the dual step is u <- proj_mu(u + sigma D(2 x_{k+1} - x_k)), the projection onto
-    the 2-norm ball of radius mu at every voxel (Backend.tv_dual_step); proxg is `wavelet_prox` when l1 > 0, that of `term`
-    (`llr_term`, whose value the objective then adds) when one is given, else the identity.
+def field_map_segments(g, mps, fmap, times, segments=None, tol=1e-3, basis=None, toeplitz=False):
+    """fmap: a real (X, Y, Z) field map in Hz, times: the sample times in seconds, (readout,) or (readout, views) -> (the field map flattened,
+    (taus, table, period, error) of `indigo_amd.fmap.segments` for `segments` segments or the fewest within `tol`), None without a field map"""
+    if fmap is None:
+        if times is not None:
+            log.info("sample times without a field map have no effect")
+        return None
+    from indigo_amd import fmap as fmap_mod
+    nro, nviews = g.samples[1:]
+    fmap = np.asarray(fmap)
+    if np.iscomplexobj(fmap):
+        raise ValueError("--fmap: the field map is complex: only a real one in Hz is supported (R2* decay in the imaginary part "
+                         "is a follow-up)")
+    if basis is not None:
+        raise ValueError("--fmap cannot be combined with --basis: the time segments take the place of the frames (a follow-up)")
+    if g.T > 1:
+        raise ValueError("--fmap cannot be combined with %d time frames: the time segments take the place of the frames (a follow-up)" % g.T)
+    if g.M > 1:
+        raise ValueError("--fmap cannot be combined with M = %d sets of maps: the segments' BlockDiag takes one image per segment "
+                         "(a follow-up)" % g.M)
+    if times is None:
+        raise ValueError("--fmap needs the sample times: give --times FILE.npy or --dwell SECONDS [--te SECONDS]")
+    fmap = fmap.reshape(fmap.shape[:3] + (-1,))[..., 0] if fmap.ndim > 3 and int(np.prod(fmap.shape[3:])) == 1 else fmap
+    if fmap.shape != g.dims:
+        raise ValueError("--fmap: the field map has shape %s, the maps have %s" % (fmap.shape, g.dims))
+    times = np.asarray(times, dtype=np.float64)
+    times = times.reshape(times.shape[:2]) if times.ndim > 2 and int(np.prod(times.shape[2:])) == 1 else times
+    if times.ndim == 2 and times.shape[1] == 1 and nviews != 1:
+        times = times[:, 0]
+    if times.shape not in ((nro,), (nro, nviews)):
+        raise ValueError("--times: the sample times have shape %s, the k-space has %d readout points and %d views: (readout,) or "
+                         "(readout, views) is expected" % (times.shape, nro, nviews))
+    mask = (np.abs(mps.reshape(g.dims + (-1,))) > 0).any(axis=3)
+    seg = fmap_mod.segments(fmap.astype(np.float32), times, L=segments, mask=mask, tol=tol)
+    if toeplitz and seg[0].size > 8:
+        raise ValueError("--toeplitz: %d time segments, at most 8 are supported: the kernel array holds 4 K^2 bytes per point of the "
+                         "doubled grid, %.1f GB here (--fmap-segments fixes their number)" % (seg[0].size, 32e-9 * seg[0].size ** 2 * g.N))
+    return fmap.reshape(-1, order='F'), seg
 
-    Steps: L is the largest eigenvalue of AHA (`power_iteration`), or 0.9 / step when `step` is given; tau = 0.9 / L and
-    sigma = L / 24 unless given.  With ||D||^2 <= 12:  1/tau - 12 sigma = L/0.9 - L/2 = 0.61 L >= L/2, the Condat-Vu condition.
 
-    frames = T > 1: x is T frames stacked, frame t in rows [tN, (t+1)N), and the penalty is mu sum_t TV(x_t) + mu_t sum_{t<T-1}
-    sum_i |x_{t+1}[i] - x_t[i]| (the wavelet term on every frame).  D is operators.GradientT, u has 4NT rows, the dual step is
-    Backend.tv4_dual_step: the spatial components onto the ball of radius mu, the temporal one onto the disc of radius mu_t.
-    With ||D4||^2 <= 16 the default sigma is L / 32:  1/tau - 16 sigma = L/0.9 - L/2 >= L/2, the same margin.  frames = 1 is
-    the iteration above unchanged (mu_t does not enter).
-    Returns the image as a host (N, 1) array and the objectives logged: [(iteration, value)], every 10 iterations and the last."""
-    c64 = np.dtype('complex64')
-    T = int(frames)
-    if T == 1:
-        comps, G, step_fn, step_args = 3, B.Gradient(dims), B.tv_dual_step, (mu, dims)
-    else:
-        comps, G, step_fn, step_args = 4, B.GradientT(dims, T), B.tv4_dual_step, (mu, mu_t, dims, T)
-    if step is None:
-        L = power_iteration(B, AHA, power_iters)
-        log.info("tv: largest eigenvalue of A^H A + lamda I %.6e (%d power iterations)", L, power_iters)
-    else:
-        L = 0.9 / step
-    tau = 0.9 / L
-    if sigma is None:
-        sigma = L / (8 * comps)
-    log.info("tv: tau %.6e, sigma %.6e, mu %g, %s", tau, sigma, mu, tuple(dims))
+def density_lookup(B, g, traj_shape, dcf, dcf_iters=30, width=3, osf=640 / 480):
+    """-> frame_density(trj3, t): the weights of trajectory trj3, frame t of the trajectory's own frames, float64 (rows,): those of the
+    array `dcf` (checked by `sample_density`), Pipe-Menon weights for dcf = 'auto', None without dcf"""
+    if dcf is None:
+        return lambda trj3, t: None
+    if isinstance(dcf, str) and dcf == 'auto':
+        from indigo_amd.dcf import pipe_menon
+        return lambda trj3, t: pipe_menon(B, trj3, g.dims, width=width, osf=osf, iters=dcf_iters).reshape(-1, order='F').astype(np.float64)
+    dens = sample_density(dcf, traj_shape)
+    if dens.shape[1] not in (1, g.T_traj):
+        raise ValueError("--dcf: the weights have %d frames, the trajectory has %d" % (dens.shape[1], g.T_traj))
+    return lambda trj3, t: dens[:, t if dens.shape[1] > 1 else 0]
+
+
+def forward_model(B, g, mps, traj, recipe, lamda=0.0, width=3, osf=640 / 480, phi=None, seg=None, frame_density=lambda trj3, t: None):
+    """The forward model of the module docstring, the scratch arena reserved for it -> (A, A^H A + lamda I, the distinct trajectories, the
+    index into them of every frame, the density weights of every distinct trajectory or None).  traj: in units of the field of view; recipe:
+    the pass list of the trees; phi: the basis of a subspace run; seg: from `field_map_segments`; frame_density: from `density_lookup`"""
+    from indigo_amd.analyses import ScratchUsage
+    from indigo_amd.transforms import Optimize, reserve_for, soft_sense_tree
+    N, C, M, T, rows = g.N, g.C, g.M, g.T, g.rows
+
+    def panel(n):                                        # a product's temporary of n rows in the arena, which carves in steps of 32
+        return (n + 31) // 32 * 32
+
+    def weighted(A, wts):
+        """W^(1/2) A: the forward model of the density-compensated data term (one weight per sample, shared by the coils)"""
+        if wts is None:
+            return A
+        WA = B.SampleWeights(np.sqrt(wts), rows, A.shape[0] // rows, name='sqrt dcf') * A
+        WA._name = A._name
+        return WA
+
+    def frame_operators(trj3, wts=None):
+        """A_t and A_t^H A_t + lamda I of one trajectory (in a temporal subspace A_t^H A_t alone: lamda acts on the coefficients);
+        wts: density-compensation weights of its samples, W^(1/2) A_t in place of A_t"""
+        def nufft():
+            return B.NUFFT(g.samples, g.dims, trj3, width=width, oversamp=(osf, osf, osf), dtype=np.dtype('complex64'))
+        if M > 1:
+            A = soft_sense_tree(B, nufft, mps.reshape(g.dims + (C, M)), recipe)
+        else:
+            A = B.KronI(C, nufft()) * B.VStack([B.Diag(mps[:, :, :, c].reshape(g.dims + (1,))) for c in range(C)], name='maps')
+            A._name = 'SENSE1'
+            A = Optimize(recipe).visit(A)
+        A = weighted(A, wts)
+        AHA = (A.H * A) + lamda * B.Eye(A.shape[1]) if phi is None else A.H * A
+        AHA._name = 'SENSE'
+        return A, AHA
+
+    # frames with equal trajectories share one tree: its matrices are built and uploaded once, and BlockDiag evaluates the
+    # same child on each of those frames' rows in turn
+    trjs = traj.reshape(traj.shape[:3] + (g.T_traj,))
+    distinct, trees, which, density = [], [], [], []
+    for t in range(T):
+        t_traj = t if g.T_traj > 1 else 0
+        trj3 = trjs[..., t_traj]
+        k = next((k for k, seen in enumerate(distinct) if np.array_equal(seen, trj3)), None)
+        if k is None:
+            k = len(distinct)
+            distinct.append(trj3)
+            density.append(frame_density(trj3, t_traj))
+            # (with a field map the weights go around the segments' combination, not into every segment's tree)
+            trees.append(frame_operators(trj3, density[-1] if seg is None else None))
+        which.append(k)
+    A, AHA = trees[0]
     if T > 1:
-        log.info("tv: %d frames, mu_t %g", T, mu_t)
-    assert term is None or not l1 > 0, "one prox slot: the wavelet term or `term`"
-    if l1 > 0:
-        term = wavelet_term(B, dims, l1, wavelet, levels)
-    if term is not None:
-        log.info("tv: %s", term.text)
-    n = AHA.shape[1]
-    b = B.copy_array(AHy, name='AHy')
-    u = B.zero_array((comps * n, 1), c64, name='tv.u')
+        log.info("frames %d, distinct trajectories %d", T, len(distinct))
+        A = B.BlockDiag([trees[k][0] for k in which], name='SENSE1 frames')
+        AHA = B.BlockDiag([trees[k][1] for k in which], name='SENSE frames')
+    # the children run one after the other on the same arena: the scratch of the most demanding one, once, and what the products around them hold
+    worst = max((tree[1] for tree in trees), key=lambda node: ScratchUsage().measure(node, 1))
+    krows = trees[0][0].shape[0]
+    extra = 0 if density[0] is None else panel(krows)    # the weighted product's extra k-space panel
+    if phi is not None:
+        # x_t = sum_k Phi[t, k] alpha_k: the unknowns are the K coefficient images.  Below the frames' trees the three-factor
+        # product holds two panels of all T frames: the synthesised frames and what the frames' operators make of them
+        Phi = B.FrameBasis(phi, N, name='basis')
+        A = A * Phi
+        A._name = 'SENSE1 subspace'
+        AHA = Phi.H * AHA * Phi + lamda * B.Eye(N * phi.shape[1])
+        AHA._name = 'SENSE subspace'
+        extra += 2 * panel(N * T)
+    if seg is not None:
+        # the L segments are L frames on one trajectory: one tree under the BlockDiag.  Around it the product holds two panels
+        # of the segments' images and two of their samples
+        field, (taus, table, period, _) = seg
+        L = taus.size
+        extra += 2 * panel(N * L) + 2 * panel(krows * L)
+    reserve_for(worst, 1, slack_products=6, extra=extra)
+    if seg is not None:
+        Phase = B.SegmentPhase(field, taus, N, name='segment phase')
+        A = B.SegmentCombine(table, period, krows, name='segment combine') * B.BlockDiag([A] * L, name='SENSE1 segments') * Phase
+        A._name = 'SENSE1 off-resonance'
+        A = weighted(A, density[0])
+        AHA = (A.H * A) + lamda * B.Eye(N)
+        AHA._name = 'SENSE off-resonance'
+    return A, AHA, distinct, which, None if density[0] is None else density
 
-    def gradf(g, z):
-        AHA.eval(g, z)
-        B.axpby(1, g, -1, b)
 
-    def KH(g, v):
-        G.eval(g, v, alpha=1, beta=1, forward=False)
+def right_hand_side(g, A, which, density, ksp):
+    """-> (y, AHy, scale, density): the k-space vector (with density weights sqrt(w) . y, frame by frame: the data of the same weighted
+    problem), A^H y divided by `scale`, its largest modulus, and the weights as the operators apply them, rounded through float32"""
+    y = np.asfortranarray(ksp.reshape((-1, 1), order='F'))
+    if density is not None:
+        sq = np.sqrt(np.stack([density[k] for k in which], axis=1)).astype(np.float32)
+        y = np.asfortranarray((y.reshape((g.rows, g.C, g.T), order='F') * sq[:, None, :]).astype(ksp.dtype).reshape((-1, 1), order='F'))
+        density = [np.square(np.sqrt(d).astype(np.float32).astype(np.float64)) for d in density]
+    AHy = A.H * y
+    scale = abs(AHy).max()
+    AHy /= scale
+    return y, AHy, scale, density
 
-    def dual_step(v, xn, xo):
-        step_fn(v, xn, xo, sigma, *step_args)
 
-    objectives = []
-    work = {}
-
-    def objective(k, x):
-        if not (k % 10 == 9 or k == iters - 1) or not log.isEnabledFor(logging.INFO):
-            return
-        if not work:
-            work['q'] = B.zero_array((n, 1), c64, name='objective.q')
-            work['d'] = B.zero_array((comps * n, 1), c64, name='objective.d')
-        q, d = work['q'], work['d']
-        AHA.eval(q, x)
-        G.eval(d, x)
-        diffs = d.to_host().reshape((n // T, comps, T), order='F').astype(np.complex128)
-        val = 0.5 * B.dot(x, q) - B.dot(x, b) + 0.5 * ynorm2 + mu * float(np.sqrt((np.abs(diffs[:, :3]) ** 2).sum(axis=1)).sum())
-        if T > 1:
-            val += mu_t * float(np.abs(diffs[:, 3]).sum())
-        if term is not None:
-            val += term.value(x)
-        objectives.append((k + 1, val))
-        log.info("tv iter %d, objective %.9e", k + 1, val)
-
-    x = np.zeros((n, 1), dtype=c64, order='F')
-    B.primal_dual(gradf, term.proxg if term is not None else None, KH, dual_step, tau, x, u, maxiter=iters, callback=objective)
-    return x, objectives
+def solve(B, g, AHA, AHy, cols, iters=20, l1=0.0, tv=0.0, tv_sigma=None, tv_time=0.0, llr=0.0, llr_block=8, llr_shifts=False, llr_seed=0, **prox):
+    """the solver that the options select (`reconstruct`'s docstring), on AHA x = AHy with `cols` images in the unknown -> x, host (n, 1).
+    prox: what `fista_solve` and `tv_solve` both take: wavelet, levels, power_iters, step, ynorm2"""
+    if tv_time > 0 and g.T == 1:
+        log.info("--tv-time %g has no effect on a scan with one time frame", tv_time)
+        tv_time = 0.0
+    term = None
+    if llr > 0:
+        term = llr_term(B, g.dims, cols, llr, block=llr_block, shifts=llr_shifts, seed=llr_seed)
+        if cols == 1:
+            log.info("--llr on a scan with one time frame: every block has rank one, the term shrinks the blocks' 2-norms")
+    if tv > 0 or tv_time > 0:
+        return tv_solve(B, AHA, AHy, g.dims, iters, tv, sigma=tv_sigma, l1=l1, frames=cols, mu_t=tv_time, term=term, **prox)[0]
+    if l1 > 0 or llr > 0:
+        return fista_solve(B, AHA, AHy, g.dims, iters, l1, term=term, **prox)[0]
+    x = np.zeros((AHA.shape[1], 1), dtype=np.complex64, order='F')
+    hist = B.cg(AHA, AHy, x, maxiter=iters)
+    log.info("residuals: %s", " ".join("%.3e" % h for h in (hist or [])))
+    return x
 
 
 def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, width=3, fuse=True,
@@ -612,241 +647,39 @@ def reconstruct(B, ksp, mps, traj, iters=20, lamda=0.0, level=3, osf=640 / 480, 
     error fmap_tol); one frame, one set of maps, no basis.  The unknown and the result are those of the plain run.
     dcf: density-compensation weights with the axes of traj without the first, or 'auto' (Pipe-Menon, dcf_iters iterations, once per
     distinct trajectory): the weighted data term of the module docstring; every solver runs unchanged on the weighted A and y."""
-    from indigo_amd.transforms import FuseZpadFFT, Optimize, sense_recipe, soft_sense_tree
-    from indigo_amd.transforms import reserve_for
-    ksp = np.asarray(ksp, dtype=np.complex64)
-    mps = np.asarray(mps, dtype=np.complex64)
-    traj = np.array(traj, dtype=np.float64)
-    ksp_nc_dims = ksp.shape
-    M = mps.shape[dim.MAPS] if mps.ndim > dim.MAPS else 1          # sets of coil maps: M > 1 is soft-SENSE, M images per frame
-    if ksp.ndim > dim.MAPS and ksp.shape[dim.MAPS] != 1:
-        raise ValueError("data has a MAPS axis of length %d: only the maps carry several sets, the k-space is one measurement "
-                         "(MAPS must be 1 in data)" % ksp.shape[dim.MAPS])
-    img_dims = mps.shape[:3] + (1,) + ksp.shape[4:]
-    if M > 1:
-        img_dims = img_dims + (1,) * (dim.MAPS + 1 - len(img_dims))
-        img_dims = img_dims[:dim.MAPS] + (M,) + img_dims[dim.MAPS + 1:]
-    log.info('img %s %s', img_dims, ksp.dtype)
-    log.info('mps %s, ksp %s, trj %s, sets of maps %d', mps.shape, ksp.shape, traj.shape, M)
+    from indigo_amd.transforms import FuseZpadFFT, sense_recipe
+    ksp, mps, traj = np.asarray(ksp, dtype=np.complex64), np.asarray(mps, dtype=np.complex64), np.array(traj, dtype=np.float64)
+    g = geometry(ksp, mps, traj)
     for i in range(3):                                   # trajectory in units of the field of view (pics.py:69-72)
-        traj[i] /= mps.shape[i]
-    C = ksp.shape[dim.COIL]
-    T = ksp.shape[dim.TIME] if ksp.ndim > dim.TIME else 1
-    if M > 1:
-        assert int(np.prod(mps.shape[dim.MAPS + 1:])) == 1, "Of the maps only COIL and MAPS may be longer than 1."
-        # soft-SENSE follow-ups (DESIGN.md §7): the unknown is ordered maps inside frames, which is not what these three take
-        if tv_time > 0:
-            raise ValueError("--tv-time cannot be combined with M = %d sets of maps: GradientT differences neighbouring columns of the "
-                             "unknown, which are then the images of one frame's sets, not neighbouring frames" % M)
-        if basis is not None:
-            raise ValueError("--basis cannot be combined with M = %d sets of maps: FrameBasis mixes the columns of the unknown as "
-                             "frames, and they are then the images of the sets inside every frame" % M)
-        if toeplitz:
-            raise ValueError("--toeplitz cannot be combined with M = %d sets of maps: ToeplitzNormal takes one set" % M)
-        if M > 4:
-            raise ValueError("%d sets of maps, at most 4 are supported (Backend.coil_maps)" % M)
-        if llr > 0 and M * T > 32:
-            raise ValueError("--llr: M * T = %d x %d = %d columns, at most 32 are supported (Backend.llr_threshold)" % (M, T, M * T))
-    assert mps.ndim <= dim.TIME or mps.shape[dim.TIME] == 1, "The maps carry no TIME axis: one set for all frames."
-    T_traj = traj.shape[dim.TIME] if traj.ndim > dim.TIME else 1
-    assert T_traj in (1, T), "traj has %d time frames, data has %d" % (T_traj, T)
-    assert int(np.prod(ksp.shape[4:])) == T and int(np.prod(traj.shape[3:])) == T_traj, "Only COIL and TIME may be longer than 1."
-    phi = None
-    if basis is not None:
-        assert not tv_time > 0, "--tv-time cannot be combined with --basis: differences between coefficients are not differences in time"
-        phi = subspace_basis(basis, T, basis_rank)
-        K = phi.shape[1]
-        img_dims = mps.shape[:3] + (1,) * (dim.COEFF - 3) + (K,)
-        gram = phi.astype(np.complex128)
-        log.info("basis: %d frames, %d coefficients, ||Phi^H Phi - I|| %.3e", T, K, np.linalg.norm(gram.conj().T @ gram - np.eye(K)))
-        if toeplitz and K > 8:
-            raise ValueError("--toeplitz: %d coefficients, at most 8 are supported: the kernel array holds 4 K^2 bytes per point of the "
-                             "doubled grid, %.1f GB here (--basis-rank keeps the first K columns)" % (K, 32e-9 * K * K * int(np.prod(mps.shape[:3]))))
-    seg = None
-    if fmap is not None:
-        from indigo_amd import fmap as fmap_mod
-        fmap = np.asarray(fmap)
-        if np.iscomplexobj(fmap):
-            raise ValueError("--fmap: the field map is complex: only a real one in Hz is supported (R2* decay in the imaginary part "
-                             "is a follow-up)")
-        if basis is not None:
-            raise ValueError("--fmap cannot be combined with --basis: the time segments take the place of the frames (a follow-up)")
-        if T > 1:
-            raise ValueError("--fmap cannot be combined with %d time frames: the time segments take the place of the frames (a follow-up)" % T)
-        if M > 1:
-            raise ValueError("--fmap cannot be combined with M = %d sets of maps: the segments' BlockDiag takes one image per segment "
-                             "(a follow-up)" % M)
-        if times is None:
-            raise ValueError("--fmap needs the sample times: give --times FILE.npy or --dwell SECONDS [--te SECONDS]")
-        fmap = fmap.reshape(fmap.shape[:3] + (-1,))[..., 0] if fmap.ndim > 3 and int(np.prod(fmap.shape[3:])) == 1 else fmap
-        if fmap.shape != tuple(mps.shape[:3]):
-            raise ValueError("--fmap: the field map has shape %s, the maps have %s" % (fmap.shape, tuple(mps.shape[:3])))
-        times = np.asarray(times, dtype=np.float64)
-        times = times.reshape(times.shape[:2]) if times.ndim > 2 and int(np.prod(times.shape[2:])) == 1 else times
-        if times.ndim == 2 and times.shape[1] == 1 and ksp.shape[2] != 1:
-            times = times[:, 0]
-        if times.shape not in ((ksp.shape[1],), tuple(ksp.shape[1:3])):
-            raise ValueError("--times: the sample times have shape %s, the k-space has %d readout points and %d views: (readout,) or "
-                             "(readout, views) is expected" % (times.shape, ksp.shape[1], ksp.shape[2]))
-        mask = (np.abs(mps.reshape(mps.shape[:3] + (-1,))) > 0).any(axis=3)
-        seg = fmap_mod.segments(fmap.astype(np.float32), times, L=fmap_segments, mask=mask, tol=fmap_tol)
-        if toeplitz and seg[0].size > 8:
-            raise ValueError("--toeplitz: %d time segments, at most 8 are supported: the kernel array holds 4 K^2 bytes per point of the "
-                             "doubled grid, %.1f GB here (--fmap-segments fixes their number)"
-                             % (seg[0].size, 32e-9 * seg[0].size ** 2 * int(np.prod(mps.shape[:3]))))
-    elif times is not None:
-        log.info("sample times without a field map have no effect")
-    recipe = sense_recipe(level)
-    if fuse and level >= 3:
-        recipe = recipe + [FuseZpadFFT]
-    rows = int(np.prod(ksp.shape[1:3]))                  # samples of one coil of one frame
-    dens = None
-    if dcf is not None and not (isinstance(dcf, str) and dcf == 'auto'):
-        dens = sample_density(dcf, traj.shape)
-        if dens.shape[1] not in (1, T_traj):
-            raise ValueError("--dcf: the weights have %d frames, the trajectory has %d" % (dens.shape[1], T_traj))
-
-    def frame_density(trj3, t):
-        """the weights of the trajectory of frame t (of the trajectory's own frames), float64 (rows,), or None without --dcf"""
-        if dcf is None:
-            return None
-        if dens is not None:
-            return dens[:, t if dens.shape[1] > 1 else 0]
-        from indigo_amd.dcf import pipe_menon
-        return pipe_menon(B, trj3, mps.shape[:3], width=width, osf=osf, iters=dcf_iters).reshape(-1, order='F').astype(np.float64)
-
-    def weighted(A, wts):
-        """W^(1/2) A: the forward model of the density-compensated data term (one weight per sample, shared by the coils)"""
-        if wts is None:
-            return A
-        name = A._name
-        A = B.SampleWeights(np.sqrt(wts), rows, A.shape[0] // rows, name='sqrt dcf') * A
-        A._name = name
-        return A
-
-    def frame_operators(trj3, wts=None):
-        """A_t and A_t^H A_t + lamda I of one trajectory (in a temporal subspace A_t^H A_t alone: lamda acts on the coefficients);
-        wts: density-compensation weights of its samples, W^(1/2) A_t in place of A_t"""
-        def nufft():
-            return B.NUFFT(ksp_nc_dims[:3], mps.shape[:3], trj3, width=width, oversamp=(osf, osf, osf), dtype=ksp.dtype)
-        if M > 1:
-            A = weighted(soft_sense_tree(B, nufft, mps.reshape(mps.shape[:3] + (C, M)), recipe), wts)
-            AHA = (A.H * A) + lamda * B.Eye(A.shape[1])
-            AHA._name = 'SENSE'
-            return A, AHA
-        F1 = nufft()
-        F = B.KronI(C, F1)
-        S = B.VStack([B.Diag(mps[:, :, :, c].reshape(mps.shape[:3] + (1,))) for c in range(C)], name='maps')
-        A = F * S
-        A._name = 'SENSE1'
-        A = weighted(Optimize(recipe).visit(A), wts)
-        AHA = (A.H * A) + lamda * B.Eye(A.shape[1]) if phi is None else A.H * A
-        AHA._name = 'SENSE'
-        return A, AHA
-
-    if T == 1:
-        distinct, which = [traj.reshape(traj.shape[:3])], [0]
-        density = [frame_density(distinct[0], 0)]
-        # (with a field map the weights go around the segments' combination, not into every segment's tree)
-        A, AHA = frame_operators(distinct[0], density[0] if seg is None else None)
-        wpanel = 0 if dcf is None else (A.shape[0] + 31) // 32 * 32          # the weighted product's extra k-space panel
-        if seg is None:
-            reserve_for(AHA, 1, slack_products=6, extra=wpanel)
-        else:
-            # the L segments are L frames on one trajectory: one tree under the BlockDiag.  Around it the product holds two panels
-            # of the segments' images and two of their samples
-            taus, table, period, _ = seg
-            N, L, krows = int(np.prod(mps.shape[:3])), taus.size, A.shape[0]
-            reserve_for(AHA, 1, slack_products=6, extra=2 * ((N * L + 31) // 32 * 32) + 2 * ((krows * L + 31) // 32 * 32) + wpanel)
-            Phase = B.SegmentPhase(fmap.reshape(-1, order='F'), taus, N, name='segment phase')
-            A = B.SegmentCombine(table, period, krows, name='segment combine') * B.BlockDiag([A] * L, name='SENSE1 segments') * Phase
-            A._name = 'SENSE1 off-resonance'
-            A = weighted(A, density[0])
-            AHA = (A.H * A) + lamda * B.Eye(N)
-            AHA._name = 'SENSE off-resonance'
-    else:
-        # frames with equal trajectories share one tree: its matrices are built and uploaded once, and BlockDiag evaluates the
-        # same child on each of those frames' rows in turn
-        trjs = traj.reshape(traj.shape[:3] + (T_traj,))
-        distinct, trees, which, density = [], [], [], []
-        for t in range(T):
-            trj3 = trjs[..., t if T_traj > 1 else 0]
-            k = next((k for k, seen in enumerate(distinct) if np.array_equal(seen, trj3)), None)
-            if k is None:
-                k = len(distinct)
-                distinct.append(trj3)
-                density.append(frame_density(trj3, t if T_traj > 1 else 0))
-                trees.append(frame_operators(trj3, density[-1]))
-            which.append(k)
-        log.info("frames %d, distinct trajectories %d", T, len(distinct))
-        A = B.BlockDiag([trees[k][0] for k in which], name='SENSE1 frames')
-        AHA = B.BlockDiag([trees[k][1] for k in which], name='SENSE frames')
-        # the children run one after the other on the same arena: the scratch of the most demanding one, once
-        from indigo_amd.analyses import ScratchUsage
-        worst = max((tree[1] for tree in trees), key=lambda node: ScratchUsage().measure(node, 1))
-        wpanel = 0 if dcf is None else (trees[0][0].shape[0] + 31) // 32 * 32   # the weighted product's extra k-space panel
-        if phi is None:
-            reserve_for(worst, 1, slack_products=6, extra=wpanel)
-        else:
-            # x_t = sum_k Phi[t, k] alpha_k: the unknowns are the K coefficient images.  Below the frames' trees the three-factor
-            # product holds two panels of all T frames: the synthesised frames and what the frames' operators make of them
-            N = int(np.prod(mps.shape[:3]))
-            Phi = B.FrameBasis(phi, N, name='basis')
-            A = A * Phi
-            A._name = 'SENSE1 subspace'
-            AHA = Phi.H * AHA * Phi + lamda * B.Eye(N * K)
-            AHA._name = 'SENSE subspace'
-            reserve_for(worst, 1, slack_products=6, extra=2 * ((N * T + 31) // 32 * 32) + wpanel)
+        traj[i] /= g.dims[i]
+    phi = check_options(g, tv_time=tv_time, l1=l1, llr=llr, basis=basis, basis_rank=basis_rank, toeplitz=toeplitz)
+    seg = field_map_segments(g, mps, fmap, times, fmap_segments, fmap_tol, basis=basis, toeplitz=toeplitz)
+    recipe = sense_recipe(level) + ([FuseZpadFFT] if fuse and level >= 3 else [])
+    frame_density = density_lookup(B, g, traj.shape, dcf, dcf_iters, width, osf)
+    A, AHA, distinct, which, density = forward_model(B, g, mps, traj, recipe, lamda, width, osf, phi, seg, frame_density)
     log.info("tree:\n%s", AHA.dump())
     log.info('using %d MB of device memory', (AHA.memusage() + 4 * AHA.shape[1] * ksp.dtype.itemsize) / 1e6)
-    y = np.asfortranarray(ksp.reshape((-1, 1), order='F'))
-    if dcf is not None:
-        # y <- sqrt(w) . y, frame by frame, before A^H y and ||y||^2: the data of the same weighted problem
-        sq = np.sqrt(np.stack([density[k] for k in which], axis=1)).astype(np.float32)
-        y = np.asfortranarray((y.reshape((rows, C, T), order='F') * sq[:, None, :]).astype(ksp.dtype).reshape((-1, 1), order='F'))
-        density = [np.square(np.sqrt(d).astype(np.float32).astype(np.float64)) for d in density]      # (what the operators apply)
-    else:
-        density = None
-    AHy = A.H * y
-    scale = abs(AHy).max()
-    AHy /= scale
+    y, AHy, scale, density = right_hand_side(g, A, which, density, ksp)
     if toeplitz:
         # the gridding operator has done its one job, the right-hand side: every solver below runs on the Toeplitz form of A^H A
         del A, AHA
-        if T > 1:
-            del trees, worst
-        B._scratch = None
+        B.release_scratch()
+        segments = None
         if seg is not None:
-            Phase = B.SegmentPhase(fmap.reshape(-1, order='F'), seg[0], int(np.prod(mps.shape[:3])), name='segment phase')
-            weights = np.tile(seg[1], (int(np.prod(ksp.shape[1:3])) // seg[2], 1))
-            AHA = toeplitz_normal(B, mps, distinct, which, None, lamda, width, osf, recipe=recipe, segments=(Phase, weights), density=density)
-        else:
-            AHA = toeplitz_normal(B, mps, distinct, which, phi, lamda, width, osf, recipe=recipe, density=density)
+            field, (taus, table, period, _) = seg
+            segments = (B.SegmentPhase(field, taus, g.N, name='segment phase'), np.tile(table, (g.rows // period, 1)))
+        AHA = toeplitz_normal(B, mps, distinct, which, phi, lamda, width, osf, recipe=recipe, segments=segments, density=density)
         log.info("tree:\n%s", AHA.dump())
-    if tv_time > 0 and T == 1:
-        log.info("--tv-time %g has no effect on a scan with one time frame", tv_time)
-        tv_time = 0.0
-    cols = M * T if phi is None else K                   # the images of the unknown: the sets' images of every frame, or the coefficient images
-    term = None
-    if llr > 0:
-        assert not l1 > 0, "--llr and --l1 cannot be combined: two non-smooth terms in one prox slot are not a prox"
-        term = llr_term(B, mps.shape[:3], cols, llr, block=llr_block, shifts=llr_shifts, seed=llr_seed)
-        if cols == 1:
-            log.info("--llr on a scan with one time frame: every block has rank one, the term shrinks the blocks' 2-norms")
-    if tv > 0 or tv_time > 0 or l1 > 0 or llr > 0:
-        ynorm2 = float(np.vdot(y, y).real) / float(scale) ** 2          # the data term of the same normalised problem
-    if tv > 0 or tv_time > 0:
-        x, _ = tv_solve(B, AHA, AHy, mps.shape[:3], iters, tv, sigma=tv_sigma, l1=l1, wavelet=wavelet, levels=levels,
-                        power_iters=power_iters, step=step, ynorm2=ynorm2, frames=cols, mu_t=tv_time, term=term)
-        return x.reshape(img_dims, order='F')
-    if l1 > 0 or llr > 0:
-        x, _ = fista_solve(B, AHA, AHy, mps.shape[:3], iters, l1, wavelet=wavelet, levels=levels, power_iters=power_iters,
-                           step=step, ynorm2=ynorm2, term=term)
-        return x.reshape(img_dims, order='F')
-    x = np.zeros((AHA.shape[1], 1), dtype=ksp.dtype, order='F')
-    hist = B.cg(AHA, AHy, x, maxiter=iters)
-    log.info("residuals: %s", " ".join("%.3e" % h for h in (hist or [])))
-    return x.reshape(img_dims, order='F')
+    # the data term of the same normalised problem, for the solvers that log their objective
+    ynorm2 = float(np.vdot(y, y).real) / float(scale) ** 2 if tv > 0 or tv_time > 0 or l1 > 0 or llr > 0 else 0.0
+    cols = g.M * g.T if phi is None else phi.shape[1]    # the images of the unknown: the sets' images of every frame, or the coefficient images
+    x = solve(B, g, AHA, AHy, cols, iters, l1, tv, tv_sigma, tv_time, llr, llr_block, llr_shifts, llr_seed,
+              wavelet=wavelet, levels=levels, power_iters=power_iters, step=step, ynorm2=ynorm2)
+    return x.reshape(g.img_dims if phi is None else g.dims + (1,) * (dim.COEFF - 3) + (cols,), order='F')
+
+
+def cropped(arr, limits):                                # arr cut to the `limits` of its axes, in the order of those axes
+    return arr[tuple(slice(0, min(n, c)) for n, c in zip(arr.shape, limits))]
 
 
 def main(argv=None, backend=None):
@@ -858,36 +691,25 @@ def main(argv=None, backend=None):
     log.info("using backend: %s", type(backend).__name__)
     extras = load_extras(args.data)                      # (before `load`, which keeps an HDF5 file open for the result)
     data, maps, traj, write = load(args.data, args.maps)
-    basis = np.load(args.basis) if args.basis is not None else None
     crops = crop_limits(args.crop)
-    ksp = data[tuple(slice(0, min(n, c)) for n, c in zip(data.shape, crops[-data.ndim:]))].T
-    mps = maps[tuple(slice(0, min(n, c)) for n, c in zip(maps.shape, crops[-maps.ndim:]))].T
-    trj = traj[tuple(slice(0, min(n, c)) for n, c in zip(traj.shape, crops[-traj.ndim:]))].T
-    fmap = np.load(args.fmap).T if args.fmap is not None else extras['fmap'].T if 'fmap' in extras else None
+    ksp, mps, trj = (cropped(a, crops[-a.ndim:]).T for a in (data, maps, traj))
+    # the keywords of `reconstruct` are the command-line options of their names, but for these: other names, or arrays for file names
+    opts = dict(vars(args), iters=args.i, level=args.recipe, fuse=not args.no_fuse, times=None,
+                basis=np.load(args.basis) if args.basis is not None else None,
+                fmap=np.load(args.fmap).T if args.fmap is not None else extras['fmap'].T if 'fmap' in extras else None)
     if args.times is not None or 'times' in extras:
         if args.dwell is not None:
             raise ValueError("--dwell cannot be combined with the scan's own `times`: the sample times come from one of them")
-        times = (np.load(args.times) if args.times is not None else extras['times']).T
+        opts['times'] = (np.load(args.times) if args.times is not None else extras['times']).T
     elif args.dwell is not None:
-        times = (args.te or 0.0) + args.dwell * np.arange(ksp.shape[1], dtype=np.float64)
-    else:
-        times = None
-    if args.dcf == 'auto':
-        dcf = 'auto'
-    elif args.dcf is not None or 'dcf' in extras:
+        opts['times'] = (args.te or 0.0) + args.dwell * np.arange(ksp.shape[1], dtype=np.float64)
+    if args.dcf != 'auto' and (args.dcf is not None or 'dcf' in extras):
         dcf = (np.load(args.dcf) if args.dcf is not None else extras['dcf']).T
-        dcf = dcf[tuple(slice(0, min(n, c)) for n, c in zip(dcf.shape, crops[-2:-dcf.ndim - 2:-1]))]      # (its axes are the trajectory's from PHS1 on)
-    else:
-        dcf = None
+        opts['dcf'] = cropped(dcf, crops[-2:-dcf.ndim - 2:-1])           # (its axes are the trajectory's from PHS1 on)
     if args.cc is not None:
         from indigo_amd import cc
         ksp, mps = cc.compress(backend, ksp, mps, V=args.cc)[:2]
-    img = reconstruct(backend, ksp, mps, trj, iters=args.i, lamda=args.lamda, level=args.recipe, osf=args.osf,
-                      width=args.width, fuse=not args.no_fuse, l1=args.l1, wavelet=args.wavelet, levels=args.levels,
-                      power_iters=args.power_iters, step=args.step, tv=args.tv, tv_sigma=args.tv_sigma, tv_time=args.tv_time,
-                      llr=args.llr, llr_block=args.llr_block, llr_shifts=args.llr_shifts, llr_seed=args.llr_seed,
-                      basis=basis, basis_rank=args.basis_rank, toeplitz=args.toeplitz,
-                      fmap=fmap, times=times, fmap_segments=args.fmap_segments, fmap_tol=args.fmap_tol, dcf=dcf, dcf_iters=args.dcf_iters)
+    img = reconstruct(backend, ksp, mps, trj, **{k: opts[k] for k in list(inspect.signature(reconstruct).parameters)[4:]})
     write(img.T)
     log.info("reconstruction complete")
     return img

@@ -62,7 +62,7 @@ def kernels(B, a, T):
 def iteration(B, a, T=4):
     """one FISTA iteration of pics --llr on T frames of bench.py's config 4 problem against T evaluations of A^H A"""
     import bench
-    from indigo_amd.pics import llr_term
+    from indigo_amd.solvers import llr_term
     from indigo_amd.sense import normal_operator
     p = bench.sense_problem(4, 256, 8)
     A = p.build_zpadfft(B)
