@@ -32,7 +32,8 @@ def _problem(N, osf, width, nspokes, seed=4, edge=False):
 
 @pytest.mark.parametrize("NC", [8, 4, 2])
 @pytest.mark.parametrize("N,osf,width,edge", [((32, 32, 32), 2.0, 2, False), ((32, 32, 32), 2.0, 2, True), ((24, 32, 40), 2.0, 3, True),
-                                              ((32, 32, 32), 1.5, 2, True), ((32, 16, 24), 2.0, 2.5, True), ((16, 13, 16), 2.0, 2, True)])
+                                              ((32, 32, 32), 1.5, 2, True), ((32, 16, 24), 2.0, 2.5, True), ((16, 13, 16), 2.0, 2, True),
+                                              ((16, 16, 16), 2.0, 4, True)])          # (half-width 4: the 8-tap instantiations)
 def test_forward_gridding_from_separable_records(hip, monkeypatch, NC, N, osf, width, edge):
     """Y = alpha G' X + beta Y over a coil-interleaved grid panel: taps computed from the records (ig_grid_gather_sep) against scipy in
     complex128 on the stored matrix, and against the stored-tap gather of the same backend"""
