@@ -720,11 +720,15 @@ class HipBackend(Backend):
             self._check(self._L.ig_fft_plan_padded(self._ctx, a3(*grid), a3(*box_lo), a3(*box_dims), int(batch),
                                                    int(layout), ctypes.byref(plan), ctypes.byref(ws)),
                         "ig_fft_plan_padded%s" % (key,))
-            if int(support_tile) != 16:
-                self._check(self._L.ig_fft_set_support_tile(plan, int(support_tile)), "ig_fft_set_support_tile")
-            for axis, c in enumerate(kshift):          # (round 6) the centred transform's modulation of an odd chirp-z axis, carried by its passes
-                if c:
-                    self._check(self._L.ig_fft_set_axis_shift(plan, axis, int(c)), "ig_fft_set_axis_shift(axis %d, %d)" % (axis, c))
+            try:
+                if int(support_tile) != 16:
+                    self._check(self._L.ig_fft_set_support_tile(plan, int(support_tile)), "ig_fft_set_support_tile")
+                for axis, c in enumerate(kshift):          # (round 6) the centred transform's modulation of an odd chirp-z axis, carried by its passes
+                    if c:
+                        self._check(self._L.ig_fft_set_axis_shift(plan, axis, int(c)), "ig_fft_set_axis_shift(axis %d, %d)" % (axis, c))
+            except Exception:
+                self._L.ig_fft_destroy(plan)               # not in self._plans yet: nobody else would free it
+                raise
             self._plans[key] = (plan, ws.value)
         return self._plans[key]
 

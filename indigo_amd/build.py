@@ -18,7 +18,7 @@ LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(HERE, "lib", "obj")
 LIBNAME = "libindigo_hip.so"
 
-SOURCES = ["ig_fft_abd0.hip", "ig_fft_abd1.hip", "ig_fft_abd2.hip", "ig_fft_abd3.hip", "ig_fft.hip", "ig_spmm.hip", "ig_spmm_bricks.hip", "ig_spmm_runs.hip", "ig_gridsep.hip", "ig_context.hip", "ig_blas.hip",
+SOURCES = ["ig_fft_abd0.hip", "ig_fft_abd1.hip", "ig_fft_abd2.hip", "ig_fft_abd3.hip", "ig_fft.hip", "ig_spmm.hip", "ig_fft_plain.hip", "ig_fft_plan.hip", "ig_spmm_bricks.hip", "ig_spmm_runs.hip", "ig_gridsep.hip", "ig_context.hip", "ig_blas.hip",
            "ig_permute.hip", "ig_wavelet.hip", "ig_tv.hip", "ig_llr.hip", "ig_basis.hip", "ig_fmap.hip", "ig_toep.hip", "ig_maps.hip", "ig_nlinv.hip", "ig_espirit.hip", "ig_cc.hip", "ig_dict.hip", "ig_epg.hip", "ig_dcf.hip", "ig_comm.hip", "ig_interp.hip", "ig_dense.hip"]       # (the slow ones first: four compile side by side)
 ARCH = "gfx950"
 CXXFLAGS = [
@@ -33,7 +33,8 @@ CXXFLAGS = [
 EXTRA_FLAGS = {
     # the SLP vectoriser pairs unrelated scalar butterfly operations into v_pk_* instructions and pays four v_mov per
     # pair to gather the operands (measured: 298 v_mov among 1942 instructions of the 512-point kernel)
-    "ig_fft.hip": os.environ.get("INDIGO_FFT_FLAGS", "-fno-slp-vectorize").split(),
+    # (all three FFT units, the host-only ig_fft_plan.hip too: its table arithmetic is compiled as it was inside ig_fft.hip)
+    **{u: os.environ.get("INDIGO_FFT_FLAGS", "-fno-slp-vectorize").split() for u in ("ig_fft.hip", "ig_fft_plain.hip", "ig_fft_plan.hip")},
     "ig_fft_abd0.hip": ["-fno-slp-vectorize"], "ig_fft_abd1.hip": ["-fno-slp-vectorize"],
     "ig_fft_abd2.hip": ["-fno-slp-vectorize"], "ig_fft_abd3.hip": ["-fno-slp-vectorize"],
     # the SLP vectoriser turns the complex products into v_pk_fma_f32 and keeps a negated and swapped copy of every loop-invariant

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdarg>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "indigo_hip.h"
@@ -42,6 +43,7 @@ struct ig_ctx {
     bool         bricks_attr = false;     // the brick-binned gridding kernel's dynamic-LDS opt-in was applied on this device
     bool         fft3d_attr = false;      // the two-launch 256^3 transform's dynamic-LDS opt-in was applied on this device
     bool         fft_w32_attr = false;    // the 32-column FFT kernels' dynamic-LDS opt-in was applied on this device
+    bool         fft_lds_attr = false;    // the multi-stage LDS FFT kernel's dynamic-LDS opt-in was applied on this device
     // profile mode (ig_prof_enable): every kernel launch is bracketed by two events
     bool                     prof_on = false;
     bool                     capturing = false;    // ig_graph_begin ... ig_graph_end / _abort: launches are recorded, not executed
@@ -166,6 +168,11 @@ static inline int64_t ig_clamp1(int64_t v, int64_t hi) { return v < 1 ? 1 : (v >
 static inline dim3 ig_grid_1d(int64_t n, int per_block, int64_t max_blocks) {
     const int64_t blocks = (n + per_block - 1) / per_block;
     return dim3((unsigned)(blocks < max_blocks ? blocks : max_blocks));
+}
+// A launch whose two arms differ in one boolean (or 0 / 1) template argument: f gets the flag as a std::bool_constant
+template <typename F>
+static inline void with_flag(bool flag, F&& f) {
+    if (flag) f(std::true_type{}); else f(std::false_type{});
 }
 
 // Raw buffer accesses: 128-bit descriptor (wave-uniform base, 2 GB window) + per-lane 32-bit byte offset + uniform

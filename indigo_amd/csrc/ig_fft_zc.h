@@ -11,7 +11,7 @@
 // of n1 * b2 * piece elements per tile.  Every (kx, ky) column keeps its slot whether the support table flags it or not: the
 // addresses are closed-form and the array is n0 * n1 * b2 * C elements, never more than the full-size array it replaces.
 //
-// Host code only, no dependency on the HIP headers: ig_fft.hip builds the pass descriptors of the y and z passes from zc_side,
+// Host code only, no dependency on the HIP headers: ig_fft_plan.hip builds the pass descriptors of the y and z passes from zc_side,
 // ig_fft_zc_offset / ig_fft_zc_size export the map, and tools/zc_layout_check.cpp walks it under the sanitizers.
 #pragma once
 #include <cstdint>

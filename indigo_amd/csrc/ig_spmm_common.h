@@ -47,12 +47,6 @@ inline void run_threads(int nt, const std::function<void(int)>& body) {
     for (auto& x : th) x.join();
 }
 
-// A launch whose two arms differ in one boolean (or 0 / 1) template argument: f gets the flag as a std::bool_constant
-template <typename F>
-inline void with_flag(bool flag, F&& f) {
-    if (flag) f(std::true_type{}); else f(std::false_type{});
-}
-
 }  // namespace
 
 // X(rows x N, column-major, leading dimension ldx; row k = panel row xperm[k] if given) -> *packed[rows][np], np = the power of two

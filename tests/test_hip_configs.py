@@ -77,7 +77,7 @@ def test_config2_fft_256_cubed_batch16(hip):
 
 @pytest.mark.parametrize("batch", [1, 3])
 def test_fft_256_cubed_two_launch_transform(hip, batch):
-    """256^3 volumes take the two-launch transform (x + y/64 | y/4 + z, indigo_amd/csrc/ig_fft.hip k_fft3d_a/_b): forward and
+    """256^3 volumes take the two-launch transform (x + y/64 | y/4 + z, indigo_amd/csrc/ig_fft_plain.hip k_fft3d_a/_b): forward and
     inverse, out of place and in place (launch A cannot run in place: the plan stages through its own buffer), vs numpy"""
     n = 256
     x = (rand64c(n, n, n, batch, seed=7) - np.complex64(0.5 + 0.5j)).astype(C64)
@@ -395,7 +395,16 @@ def test_config5_as_benchmarked_on_one_gpu(hip, oracle_backend):
                                         ((400, 432, 512), (300, 310, 256), 4),
                                         # lengths of the generated list (tools/gen_ab_list.py): odd ones, splits with A != B, 3 / 5 / 7 in both factors
                                         ((288, 270, 392), (208, 208, 308), 4), ((600, 135, 175), (480, 100, 140), 2),
-                                        ((144, 625, 128), (100, 500, 96), 16), ((360, 250, 567), (256, 200, 400), 2)])
+                                        ((144, 625, 128), (100, 500, 96), 16), ((360, 250, 567), (256, 200, 400), 2),
+                                        # a 256- or 512-point x axis: the weighted and coil-summing x passes of k_fft_2stage (its lane split = the
+                                        # coil count) with the compile-time half box (256 in 512, 128 in 256) and with a run-time box, on the
+                                        # smallest y and z axes the layout takes
+                                        ((512, 128, 128), (256, 96, 96), 2), ((512, 128, 128), (320, 96, 96), 2), ((512, 128, 128), (256, 96, 96), 4),
+                                        ((512, 128, 128), (256, 64, 64), 16), ((512, 128, 128), (320, 64, 64), 16),
+                                        ((256, 128, 128), (128, 64, 64), 16), ((256, 128, 128), (160, 64, 64), 16), ((256, 128, 128), (160, 96, 96), 8),
+                                        # one coil (all axes 256 points: the A x B passes take two coils or more)
+                                        ((256, 256, 256), (128, 128, 128), 1), ((256, 256, 256), (160, 160, 160), 1),
+                                        ((512, 256, 256), (256, 128, 128), 1), ((512, 256, 256), (320, 160, 160), 1)])
 def test_padded_transforms_on_non_power_of_two_grids_vs_numpy(hip, grid, box, C):
     """fft_padded / ifft_cropped / ifft_cropped_sum (layout 2) on grids whose axes are 320 ... 640 points long (and mixed
     with 512): one coil of the forward grid against numpy, the cropped inverse and the coil combination against their
@@ -412,7 +421,7 @@ def test_padded_transforms_on_non_power_of_two_grids_vs_numpy(hip, grid, box, C)
     y_d = hip.copy_array(np.full((P, C), np.nan, dtype=C64, order='F'))
     hip.fft_padded(y_d, hip.copy_array(x), w_d, grid, lo, box, ws, 2)
     y = y_d.to_host().reshape(-1, order='F').reshape((C, grid[0], grid[2], grid[1]), order='F')        # (c, x, z, y)
-    for c in (0, C - 1):
+    for c in sorted({0, C - 1}):
         full = np.zeros(grid, dtype=C64, order='F')
         full[sl] = (w[:, c] * x[:, 0]).reshape(box, order='F')
         ref = np.fft.fftn(full)

@@ -278,6 +278,11 @@ def _from_layout(flat, grid, layout):
     ((512, 256, 256), (128, 200, 32), None, 4, False, 2),
     ((256, 256, 512), (64, 31, 256), None, 16, True, 2),
     ((256, 256, 256), (128, 128, 128), None, 1, True, 2),
+    # unweighted x passes (w = None) of k_fft_2stage that the cases above leave out: a run-time box on contiguous 256-point lines; the
+    # compile-time half box of a 512-point x axis on contiguous lines and, with the coils below x, at a stride
+    ((256, 256, 256), (160, 160, 160), None, 1, False, 0),
+    ((512, 256, 256), (256, 128, 128), None, 1, False, 1),
+    ((512, 256, 256), (256, 128, 128), None, 1, False, 2),
 ])
 def test_padded_and_cropped_fft_leaves(hip, grid, box, lo, C, weighted, layout):
     """fft_padded == fftn(zero-pad(w*x)) and ifft_cropped == conj(w)*crop(ifftn(y)), both computed on the GPU

@@ -1,6 +1,6 @@
 """The address map of the z-contiguous y <-> z intermediate (indigo_amd/csrc/ig_fft_zc.h), on the host: no GPU.
 
-ig_fft_zc_offset / ig_fft_zc_size are the map the pass schedule of ig_fft.hip is built from.  Checked here through the library
+ig_fft_zc_offset / ig_fft_zc_size are the map the pass schedule of ig_fft_plan.hip is built from.  Checked here through the library
 on the planes where an error would show (first, second and last ky and z, every (kx, coil)), and in full -- every element of
 every shape, both passes walked the way the kernel's workgroups address them -- by tools/zc_layout_check.cpp, a stand-alone
 program built with the address and undefined-behaviour sanitizers."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Thread-level numpy model of the two-launch 256^3 FFT (k_fft3d_a / k_fft3d_b in indigo_amd/csrc/ig_fft2.hip).
+"""Thread-level numpy model of the two-launch 256^3 FFT (k_fft3d_a / k_fft3d_b in indigo_amd/csrc/ig_fft_plain.hip).
 
 Not product code: a CPU rehearsal of the kernels' index maps -- every load, every register DFT, every LDS exchange
 with its exact addresses -- so that the arithmetic (digit orders, twiddles, exchanges) and the LDS bank behaviour are
