@@ -2251,7 +2251,8 @@ int ig_ccsrmm_t_slots(ig_ctx* ctx, int64_t M, int64_t K, int64_t N, float ar, fl
     IG_REQUIRE(ctx, M >= 0 && K >= 0 && M <= 0x7fffffffLL, "ig_ccsrmm_t_slots: bad dimensions");
     IG_REQUIRE(ctx, N == 1 || N == 2 || N == 4, "ig_ccsrmm_t_slots: 1, 2 or 4 columns (got %lld; at 8 the round format of ig_ccsrmm_t_bricks is faster: 0.77 against 1.28 ms)", (long long)N);
     IG_REQUIRE(ctx, (ntasks == 0 || (entries16 && slot_ptr)) && (M == 0 || X) && (K == 0 || Y_il) && ldx >= M, "ig_ccsrmm_t_slots: NULL array or short leading dimension");
-    IG_REQUIRE(ctx, n0 > 0 && nm > 0 && K % (n0 * nm) == 0 && K < 0x7fffffffLL && bricks_ok(n0, nm, K / (n0 * nm), bm, bs, 1) && bm * bs <= 32,
+    // (K == 0: an empty grid has no slow axis to divide into bricks, and nothing to do)
+    IG_REQUIRE(ctx, n0 > 0 && nm > 0 && K % (n0 * nm) == 0 && K < 0x7fffffffLL && (K == 0 || bricks_ok(n0, nm, K / (n0 * nm), bm, bs, 1)) && bm * bs <= 32,
                "ig_ccsrmm_t_slots: rows (%lld) are not a grid of n0=%lld x nm=%lld x ... that divides into 16 x %d x %d bricks", (long long)K, (long long)n0, (long long)nm, bm, bs);
     const int64_t ns = K / (n0 * nm);
     IG_REQUIRE(ctx, !support || (zw <= 64 && nm <= 32 * (int64_t)zw), "ig_ccsrmm_t_slots: the support bitmaps hold 32 bits in each of %d words: nm <= %d", zw, 32 * zw);
