@@ -111,7 +111,12 @@ class HipBackend(Backend):
     def set_option(self, name, value):
         """plan options of the library (ig_set_option): 'fft.kernels' = 0 all kernels, 1 no A x B passes, 2 generic stages only;
         'fft.zc_intermediate' = 1 the fused SENSE leaf keeps what its y and z passes exchange z-contiguous per kx tile, 0 in the
-        grid's own order (bit-identical results, same workspace); takes effect for plans made afterwards (cached plans are dropped)"""
+        grid's own order (bit-identical results, same workspace); 'fft.xy_chunk_planes' = K > 0 the fused SENSE leaf (grid layout 2,
+        256- / 512-point x and y axes) runs its x and y passes chunk by chunk over K image planes, so that what they exchange is
+        re-read while it is still in the last-level cache, 0 one launch per pass, -1 (the default) as many planes as make 128 MiB
+        of what they exchange (16 on the 512^3 x 8 grid; problems below that size keep one launch per pass); 'fft.xy_chunk_streams' = S in 1, 2, 3: chunk i
+        runs on stream i mod S (default 2), joined back into the backend's stream before the call returns (bit-identical results either way;
+        ignored while a graph is recorded); takes effect for plans made afterwards (cached plans are dropped)"""
         self._check(self._L.ig_set_option(self._ctx, name.encode(), int(value)), "ig_set_option(%s)" % name)
         for entry in self._plans.values():
             self._L.ig_fft_destroy(entry[0])

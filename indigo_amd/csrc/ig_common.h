@@ -11,7 +11,7 @@
 
 #include "indigo_hip.h"
 
-// one timed kernel launch (profile mode): events recorded on the context's stream
+// one timed kernel launch (profile mode): events recorded on the stream of the launch (the context's, unless the scope names another)
 struct ig_prof_rec {
     const char* name;
     double      bytes;     // caller-supplied algorithmic bytes of this launch (0 if not given)
@@ -40,6 +40,13 @@ struct ig_ctx {
     // "fft.zc_intermediate" (read by every zero-padded / cropped transform, not only by new plans): 1 = the fused SENSE leaf keeps
     // what its y and z passes exchange z-contiguous per kx tile (ig_fft_zc.h), 0 = in the grid's own order
     int          opt_fft_zc = 1;
+    // "fft.xy_chunk_planes" / "fft.xy_chunk_streams" (read by every zero-padded / cropped transform): the fused SENSE leaf runs its
+    // x and y passes chunk by chunk over K image planes, chunk i on stream i mod S (ig_fft_xy.h); K = 0: one launch per pass; K = -1:
+    // as many planes as make 128 MiB of the intermediate -- 16 on the 512^3 x 8 grid, the (K, S) = (16, 2) that passed the keep gate
+    // there (profiles/xy_chunks_ab.txt)
+    int          opt_fft_xy_planes = -1, opt_fft_xy_streams = 2;
+    hipStream_t  xy_stream[2] = {nullptr, nullptr};     // the streams behind ctx->stream, made on first use (xy_fork, ig_fft_plan.hip)
+    hipEvent_t   xy_fork = nullptr, xy_join[2] = {nullptr, nullptr};
     bool         bricks_attr = false;     // the brick-binned gridding kernel's dynamic-LDS opt-in was applied on this device
     bool         fft3d_attr = false;      // the two-launch 256^3 transform's dynamic-LDS opt-in was applied on this device
     bool         fft_w32_attr = false;    // the 32-column FFT kernels' dynamic-LDS opt-in was applied on this device
@@ -53,8 +60,8 @@ struct ig_ctx {
 
 // RAII bracket around a kernel launch; a no-op unless profile mode is on.
 struct ig_prof_scope {
-    ig_ctx* ctx; size_t idx; bool on;
-    ig_prof_scope(ig_ctx* c, const char* name, double bytes = 0.0) : ctx(c), idx(0), on(c && c->prof_on) {
+    ig_ctx* ctx; size_t idx; bool on; hipStream_t stream;
+    ig_prof_scope(ig_ctx* c, const char* name, double bytes = 0.0, hipStream_t s = nullptr) : ctx(c), idx(0), on(c && c->prof_on), stream(s ? s : c ? c->stream : nullptr) {
         if (!on) return;
         ig_prof_rec r; r.name = name; r.bytes = bytes;
         auto get = [&]() { hipEvent_t e = nullptr;
@@ -62,11 +69,11 @@ struct ig_prof_scope {
             else (void)hipEventCreate(&e);
             return e; };
         r.e0 = get(); r.e1 = get();
-        (void)hipEventRecord(r.e0, ctx->stream);
+        (void)hipEventRecord(r.e0, stream);
         idx = ctx->prof.size();
         ctx->prof.push_back(r);
     }
-    ~ig_prof_scope() { if (on) (void)hipEventRecord(ctx->prof[idx].e1, ctx->stream); }
+    ~ig_prof_scope() { if (on) (void)hipEventRecord(ctx->prof[idx].e1, stream); }
 };
 
 struct ig_graph {

@@ -97,6 +97,11 @@ void ig_destroy(ig_ctx* ctx) {
     if (ctx->d_xpack) (void)hipFree(ctx->d_xpack);
     if (ctx->d_epg) (void)hipFree(ctx->d_epg);
     if (ctx->h_result) (void)hipHostFree(ctx->h_result);
+    for (int i = 0; i < 2; ++i) {          // (their work was joined into ctx->stream, which has been synchronised)
+        if (ctx->xy_stream[i]) (void)hipStreamDestroy(ctx->xy_stream[i]);
+        if (ctx->xy_join[i]) (void)hipEventDestroy(ctx->xy_join[i]);
+    }
+    if (ctx->xy_fork) (void)hipEventDestroy(ctx->xy_fork);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -199,6 +204,16 @@ int ig_set_option(ig_ctx* ctx, const char* name, int64_t value) {
     if (std::string(name) == "fft.zc_intermediate") {
         IG_REQUIRE(ctx, value == 0 || value == 1, "ig_set_option: fft.zc_intermediate is 0 (the grid's order) or 1 (z-contiguous per kx tile)");
         ctx->opt_fft_zc = (int)value;
+        return IG_OK;
+    }
+    if (std::string(name) == "fft.xy_chunk_planes") {
+        IG_REQUIRE(ctx, value >= -1 && value <= 0x7fffffffLL, "ig_set_option: fft.xy_chunk_planes is 0 (one launch per pass), the image planes per chunk of the x / y pair, or -1 (chunks of 128 MiB)");
+        ctx->opt_fft_xy_planes = (int)value;
+        return IG_OK;
+    }
+    if (std::string(name) == "fft.xy_chunk_streams") {
+        IG_REQUIRE(ctx, value >= 1 && value <= 3, "ig_set_option: fft.xy_chunk_streams is 1, 2 or 3 (the context's stream and up to two more)");
+        ctx->opt_fft_xy_streams = (int)value;
         return IG_OK;
     }
     return ig_fail(ctx, IG_ERR_ARG, "ig_set_option: unknown option '%s'", name);

@@ -52,11 +52,13 @@ namespace {
 //   2: output half, input box at run time      4: output half, input full
 // Half inputs prune the first butterfly layer; compile-time boxes need no predicates or bounds registers.
 // Loads and stores carry the non-temporal (streaming) hint: every byte of a pass is touched exactly once.
-template <int R1, int R2, int T, int W, bool AXIS0, int WMODE, bool BOXED, int HALF>
+// KEEP_ST: the stores take the default cache policy instead -- the first pass of a chunk of the x / y pair (ig_fft_xy.h), whose
+// output the chunk's second pass reads back a few launches later (measured: DESIGN.md section 3.1; the loads stay streaming).
+template <int R1, int R2, int T, int W, bool AXIS0, int WMODE, bool BOXED, int HALF, bool KEEP_ST = false>
 __global__ void __launch_bounds__(W * T, (!AXIS0 && R1 == 32 && (W == 32 || HALF == 1 || HALF == 3)) ? 4 : 1)
 k_fft_2stage(PassDesc d, const float2* __restrict__ tw) {
     constexpr int n = R1 * R2, B1 = R2 / T, B2 = R1 / T, NT = W * T;
-    constexpr bool NT_LD = true, NT_ST = true;      // streaming hints on both sides
+    constexpr bool NT_LD = true, NT_ST = !KEEP_ST;      // streaming hints on both sides (KEEP_ST: on the loads only)
     constexpr bool HALF_IN = HALF == 1 || HALF == 3, HALF_OUT = HALF == 2 || HALF == 4;
     constexpr int SUMW = WMODE >= 3 ? (1 << (WMODE - 3)) : 0;       // WMODE 3 + log2(coils): 3 -> 1 (no sum), 4 -> 2, 5 -> 4, 6 -> 8, 7 -> 16
     // direction: the half-input variants only serve forward (zero-padded) passes and the half-output variants only
@@ -404,16 +406,21 @@ template <typename... P> struct V2List {};
 using V2_BOXED = V2List<V2<0, 0>, V2<0, 1>, V2<0, 2>, V2<0, 3>, V2<0, 4>, V2<1, 0>, V2<1, 3>, V2<2, 0>, V2<2, 4>>;
 using V2_SUM = V2List<V2<3, 0>, V2<3, 4>, V2<4, 0>, V2<4, 4>, V2<5, 0>, V2<5, 4>, V2<6, 0>, V2<6, 4>, V2<7, 0>, V2<7, 4>>;
 using V2_W32 = V2List<V2<0, 0>, V2<0, 1>, V2<0, 2>, V2<0, 3>, V2<0, 4>>;
-// the boxed kernel <R1, 16, 16, W, AXIS0, wm, true, half> if the list has the pair, else nullptr
-template <int R1, int W, bool AXIS0, int... WM, int... HF>
+// ... with stores of the default cache policy (KEEP_ST): what writes the x <-> y intermediate -- the weighted padded x pass and the
+// cropped (inverse) y pass, strided passes both
+using V2_KEEP = V2List<V2<0, 0>, V2<0, 2>, V2<0, 4>, V2<1, 0>, V2<1, 3>>;
+using V2_W32_KEEP = V2List<V2<0, 0>, V2<0, 2>, V2<0, 4>>;
+// the boxed kernel <R1, 16, 16, W, AXIS0, wm, true, half, KEEP> if the list has the pair, else nullptr
+template <int R1, int W, bool AXIS0, bool KEEP = false, int... WM, int... HF>
 static Kernel2S pick_2stage(V2List<V2<WM, HF>...>, int wm, int half) {
     Kernel2S k = nullptr;
-    ((wm == WM && half == HF ? (void)(k = &k_fft_2stage<R1, 16, 16, W, AXIS0, WM, true, HF>) : (void)0), ...);
+    ((wm == WM && half == HF ? (void)(k = &k_fft_2stage<R1, 16, 16, W, AXIS0, WM, true, HF, KEEP>) : (void)0), ...);
     return k;
 }
 
-// launch one 2-stage axis pass (n in {256, 512}); axis0 selects the lane mapping for contiguous columns
-int ig_launch_2stage(ig_ctx* ctx, const AxisPlan& ax, const PassDesc& d_in, bool axis0, int wmode) {
+// launch one 2-stage axis pass (n in {256, 512}); axis0 selects the lane mapping for contiguous columns; stream: null = the context's;
+// keep_out: store with the default cache policy where the pass has such an instantiation (a hint: the results are the same)
+int ig_launch_2stage(ig_ctx* ctx, const AxisPlan& ax, const PassDesc& d_in, bool axis0, int wmode, hipStream_t stream, bool keep_out) {
     PassDesc d = d_in;
     if (d.ncols == 0) return IG_OK;
     IG_REQUIRE(ctx, !d.tile_bits || d.tile_words == 16 || d.tile_words == 0, "ig_fft: the two-stage kernel reads support bitmaps of 16 words per entry (got %d)", d.tile_words);
@@ -432,11 +439,15 @@ int ig_launch_2stage(ig_ctx* ctx, const AxisPlan& ax, const PassDesc& d_in, bool
         grid = pass_grid(d, d.ext0 / 32); block = dim3(512);
         lds = ((size_t)16 * 16 * 32 + 512) * 8;
         if (!ctx->fft_w32_attr) {          // per context (= per device): the attribute is a per-device property
-            for (int h = 0; h <= 4; ++h)
+            for (int h = 0; h <= 4; ++h) {
                 IG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(pick_2stage<32, 32, false>(V2_W32{}, 0, h)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                if (Kernel2S kk = pick_2stage<32, 32, false, true>(V2_W32_KEEP{}, 0, h))
+                    IG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            }
             ctx->fft_w32_attr = true;
         }
-        k = pick_2stage<32, 32, false>(V2_W32{}, 0, half);
+        if (keep_out) k = pick_2stage<32, 32, false, true>(V2_W32_KEEP{}, 0, half);
+        if (!k) k = pick_2stage<32, 32, false>(V2_W32{}, 0, half);
     } else {
         IG_REQUIRE(ctx, wmode != 3 || (!axis0 && d.cw >= 1), "ig_fft: the coil-summing pass is a strided pass with a lane split");
         const int wm = wmode == 3 ? 3 + d.cw_log2 : wmode;      // (cw is 1, 2, 4, 8 or 16: it divides the tile's 16 columns)
@@ -444,12 +455,15 @@ int ig_launch_2stage(ig_ctx* ctx, const AxisPlan& ax, const PassDesc& d_in, bool
             constexpr int R1 = decltype(n512)::value ? 32 : 16;
             constexpr bool A0 = decltype(a0)::value;
             if (!boxed && wm == 0) k = &k_fft_2stage<R1, 16, 16, 16, A0, 0, false, 0>;
-            else if (wm < 3) k = pick_2stage<R1, 16, A0>(V2_BOXED{}, wm, half);
+            else if (wm < 3) {
+                if constexpr (!A0) { if (keep_out) k = pick_2stage<R1, 16, false, true>(V2_KEEP{}, wm, half); }
+                if (!k) k = pick_2stage<R1, 16, A0>(V2_BOXED{}, wm, half);
+            }
             else if constexpr (!A0) k = pick_2stage<R1, 16, false>(V2_SUM{}, wm, half);
         }); });
     }
     IG_REQUIRE(ctx, k, "ig_fft: no two-stage kernel for weight mode %d", wmode);
-    hipLaunchKernelGGL(k, grid, block, lds, ctx->stream, d, ax.d_tw);
+    hipLaunchKernelGGL(k, grid, block, lds, stream ? stream : ctx->stream, d, ax.d_tw);
     IG_LAUNCH_CHECK(ctx, "k_fft_2stage");
     return IG_OK;
 }

@@ -88,8 +88,10 @@ struct ig_fft {
     int64_t box_lo[3] = {0, 0, 0}, box_dims[3] = {1, 1, 1};
 };
 
-// ---- ig_fft.hip: one two-stage axis pass (n in {256, 512}); axis0 selects the lane mapping for contiguous columns
-int ig_launch_2stage(ig_ctx* ctx, const AxisPlan& ax, const PassDesc& d, bool axis0, int wmode);
+// ---- ig_fft.hip: one two-stage axis pass (n in {256, 512}); axis0 selects the lane mapping for contiguous columns; stream: the
+// stream of the launch where it is not the context's, keep_out: stores of the default cache policy instead of streaming ones (the
+// chunked x / y pair, ig_fft_xy.h)
+int ig_launch_2stage(ig_ctx* ctx, const AxisPlan& ax, const PassDesc& d, bool axis0, int wmode, hipStream_t stream = nullptr, bool keep_out = false);
 // which instantiation such a pass takes: whether it is boxed, its compile-time half box; returns whether it runs on 32-column tiles
 bool ig_two_stage_variant(const AxisPlan& ax, const PassDesc& d, bool axis0, int wmode, bool& boxed, int& half);
 // the launch grid of a pass kernel at cpt columns per tile, after the checks of the tile count and the 2 GB descriptor window
