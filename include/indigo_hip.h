@@ -232,6 +232,33 @@ int  ig_grad4h_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t nt, 
  * of its own.  mu, mu_t >= 0 (0 gives exact zeros in that part); u must overlap neither xn nor xo (xn may be xo).             */
 int  ig_tv4_dual_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t nt, const void* xn, int64_t ldxn,
                      const void* xo, int64_t ldxo, float sigma, float mu, float mu_t, void* u, int64_t ldu);
+/* Second-order total generalized variation (operators.SymGradient, Backend.symgrad3 / tgv_adjoint / tgv_dual_step, pics --tgv;
+ * DESIGN.md §3.20).  No reference counterpart.  A column of v is a 3-component field on the F-ordered n0 x n1 x n2 volume of N
+ * voxels, component a in rows [aN, (a+1)N); a column of q holds the six components xx, yy, zz, xy, xz, yz of a symmetric tensor,
+ * component c in rows [cN, (c+1)N).  With D_a as above and the backward difference B_a = -D_a^H,
+ *   (B_a w)[i] = (i_a < n_a - 1 ? w[i] : 0) - (i_a > 0 ? w[i - e_a] : 0):
+ *   (E v)_aa = B_a v_a,   (E v)_ab = (B_b v_a + B_a v_b) / sqrt(2)  (a < b, stored once: the 2-norm of the six is the Frobenius norm),
+ *   (E^H q)_a = -D_a q_aa - sum_{b != a} D_b q_ab / sqrt(2).
+ * ig_symgrad3_c64:   y[:, j] = beta*y[:, j] + alpha * E v[:, j]     (y: 6N x ncols, ldy >= 6N; v: 3N x ncols, ldv >= 3N)
+ * ig_symgrad3h_c64:  y[:, j] = beta*y[:, j] + alpha * E^H q[:, j]   (y: 3N x ncols; q: 6N x ncols)
+ * beta == 0: y is not read.  An output panel that overlaps an input panel is IG_ERR_ARG.  72 bytes per voxel and column.      */
+int  ig_symgrad3_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t ncols, const void* v, int64_t ldv,
+                     float alpha_re, float alpha_im, float beta_re, float beta_im, void* y, int64_t ldy);
+int  ig_symgrad3h_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t ncols, const void* q, int64_t ldq,
+                      float alpha_re, float alpha_im, float beta_re, float beta_im, void* y, int64_t ldy);
+/* K^H (p; q) = (D^H p; E^H q - p) of K (x; v) = (D x - v; E v) in one pass:  gx[:, j] += D^H p[:, j]  (gx: N x ncols, read and
+ * written),  gv[:, j] = E^H q[:, j] - p[:, j]  (gv: 3N x ncols, written and not read);  p: 3N x ncols, q: 6N x ncols.  gx and gv
+ * must overlap neither p, q nor one another.  112 bytes per voxel and column.                                                  */
+int  ig_tgv_kh_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t ncols, const void* p, int64_t ldp,
+                   const void* q, int64_t ldq, void* gx, int64_t ldgx, void* gv, int64_t ldgv);
+/* The dual step of TGV^2 in place on p and q, one pass, with w_x = 2*xn - xo (N x ncols) and w_v = 2*vn - vo (3N x ncols):
+ *   p[:, j] <- proj_{a1}(p[:, j] + sigma * (D w_x - w_v)[:, j]),    q[:, j] <- proj_{a0}(q[:, j] + sigma * E w_v[:, j]):
+ * per voxel the three components of p are scaled by (r <= a1 ? 1 : a1 / r), r their 2-norm, and the six of q likewise with a0.
+ * a1, a0 >= 0 (0 gives exact zeros); p and q must overlap none of xn, xo, vn, vo nor one another (xn may be xo, vn may be vo).
+ * 208 bytes per voxel and column.                                                                                              */
+int  ig_tgv_dual_c64(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t ncols, const void* xn, int64_t ldxn,
+                     const void* xo, int64_t ldxo, const void* vn, int64_t ldvn, const void* vo, int64_t ldvo,
+                     float sigma, float a1, float a0, void* p, int64_t ldp, void* q, int64_t ldq);
 /* Block-wise singular-value thresholding and nuclear norms of the N x nt frame panel x: the proximal map and the value of the
  * locally low-rank penalty (Backend.llr_threshold / llr_norm, pics --llr).  No reference counterpart.  The block
  * sides b_a >= 1 are clamped to n_a, the shift is 0 <= s_a < b_a (of the clamped side).  Voxel i has the shifted coordinates

@@ -82,6 +82,14 @@ PROTOTYPES = {
                                    c_float, c_float, c_float, c_float, c_void_p, c_int64]),
     "ig_tv4_dual_c64":    (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                    c_float, c_float, c_float, c_void_p, c_int64]),
+    "ig_symgrad3_c64":    (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64,
+                                   c_float, c_float, c_float, c_float, c_void_p, c_int64]),
+    "ig_symgrad3h_c64":   (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64,
+                                   c_float, c_float, c_float, c_float, c_void_p, c_int64]),
+    "ig_tgv_kh_c64":      (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                   c_void_p, c_int64, c_void_p, c_int64]),
+    "ig_tgv_dual_c64":    (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                   c_void_p, c_int64, c_void_p, c_int64, c_float, c_float, c_float, c_void_p, c_int64, c_void_p, c_int64]),
     "ig_llr_svt_c64":     (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
                                    c_float, c_void_p, c_int64]),
     "ig_llr_nuc_c64":     (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,

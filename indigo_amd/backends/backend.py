@@ -96,6 +96,54 @@ def _grad_adjoint(t):
     return out
 
 
+def _back_diff(w, a):
+    """B_a w = -D_a^H w along axis a < 3 of w: (i_a < n_a - 1 ? w[i] : 0) - (i_a > 0 ? w[i - e_a] : 0)"""
+    w = np.moveaxis(w, a, 0)
+    out = np.zeros_like(w)
+    out[:-1] += w[:-1]
+    out[1:] -= w[:-1]
+    return np.moveaxis(out, 0, a)
+
+
+def _fwd_diff(w, a):
+    """D_a w along axis a < 3 of w: w[i + e_a] - w[i] where i_a < n_a - 1, else 0"""
+    w = np.moveaxis(w, a, 0)
+    out = np.zeros_like(w)
+    out[:-1] = w[1:] - w[:-1]
+    return np.moveaxis(out, 0, a)
+
+
+_SYM_PAIRS = ((0, 1), (0, 2), (1, 2))                     # the off-diagonal components xy, xz, yz of Backend.symgrad3, after xx, yy, zz
+
+
+def _symgrad_forward(v):
+    """E v for v of shape dims + (3, ncols): shape dims + (6, ncols), the 6N-row columns of Backend.symgrad3"""
+    out = np.zeros(v.shape[:3] + (6,) + v.shape[4:], dtype=v.dtype)
+    for a in range(3):
+        out[:, :, :, a] = _back_diff(v[:, :, :, a], a)
+    for c, (a, b) in enumerate(_SYM_PAIRS):
+        out[:, :, :, 3 + c] = (_back_diff(v[:, :, :, a], b) + _back_diff(v[:, :, :, b], a)) / np.sqrt(2.0)
+    return out
+
+
+def _symgrad_adjoint(q):
+    """E^H q for q of shape dims + (6, ncols): shape dims + (3, ncols)"""
+    out = np.zeros(q.shape[:3] + (3,) + q.shape[4:], dtype=q.dtype)
+    for a in range(3):
+        out[:, :, :, a] -= _fwd_diff(q[:, :, :, a], a)
+    for c, (a, b) in enumerate(_SYM_PAIRS):
+        out[:, :, :, a] -= _fwd_diff(q[:, :, :, 3 + c], b) / np.sqrt(2.0)
+        out[:, :, :, b] -= _fwd_diff(q[:, :, :, 3 + c], a) / np.sqrt(2.0)
+    return out
+
+
+def _ball(t, radius):
+    """t of shape dims + (comps, ncols) scaled per voxel and column onto the 2-norm ball of `radius` over its components"""
+    r = np.sqrt((t.real ** 2 + t.imag ** 2).sum(axis=3, keepdims=True))
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return t * np.where(r <= float(radius), 1.0, float(radius) / r)
+
+
 def dwt_coarse_box(dims, wavelet, levels):
     """the coarse (approximation) box that `dwt_plan` leaves: the part of the coefficients soft_threshold keeps"""
     return dwt_plan(dims, wavelet, levels)[1]
@@ -489,6 +537,11 @@ class Backend(object):
         """the forward-difference gradient of an F-ordered `dims` volume, shape (3N, N) (see operators.Gradient); .H is its adjoint"""
         return op.Gradient(self, dims, **kwargs)
 
+    def SymGradient(self, dims, **kwargs):
+        """the symmetrised backward difference of a 3-component field on an F-ordered `dims` volume, shape (6N, 3N) (see
+        operators.SymGradient); .H is its adjoint"""
+        return op.SymGradient(self, dims, **kwargs)
+
     def GradientT(self, dims, frames, **kwargs):
         """the gradient of `frames` time frames of a `dims` volume with the forward difference between neighbouring frames as a
         fourth component, shape (4NT, NT) (see operators.GradientT); .H is its adjoint"""
@@ -756,6 +809,58 @@ class Backend(object):
         assert T >= 1 and xn.size == n * T and xo.size == n * T and u.size == 4 * n * T and mu >= 0 and mu_t >= 0, \
             (u.shape, xn.shape, xo.shape, dims, frames, mu, mu_t)
         self._tv_dual_host(u, xn, xo, sigma, (mu, mu_t), dims, T)
+
+    def symgrad3(self, y, v, dims, adjoint=False, alpha=1, beta=0):
+        """y[:, j] = beta*y[:, j] + alpha * E v[:, j] (adjoint: E^H v[:, j]) for every column j.  E is the symmetrised backward
+        difference of a 3-component field on an F-ordered `dims` volume of N voxels (component a in rows [aN, (a+1)N) of a 3N-row
+        column): with B_a = -D_a^H, (B_a w)[i] = (i_a < n_a - 1 ? w[i] : 0) - (i_a > 0 ? w[i - e_a] : 0), the six components xx,
+        yy, zz, xy, xz, yz (component c in rows [cN, (c+1)N) of a 6N-row column) are (E v)_aa = B_a v_a and (E v)_ab = (B_b v_a +
+        B_a v_b) / sqrt(2), so that their 2-norm is the Frobenius norm of the symmetric tensor.  beta == 0: y is
+        not read; y must not overlap v.  This host form computes in float64 through to_host / copy_from, so that every backend
+        has it; device backends override it."""
+        dims = tuple(int(n) for n in dims)
+        n = int(np.prod(dims))
+        comps_v, comps_y = (6, 3) if adjoint else (3, 6)
+        assert v.size % (comps_v * n) == 0 and v.size // comps_v * comps_y == y.size, (v.shape, y.shape, dims)
+        ncols = v.size // (comps_v * n)
+        t = v.to_host().reshape(dims + (comps_v, ncols), order='F').astype(np.complex128)
+        out = (_symgrad_adjoint(t) if adjoint else _symgrad_forward(t)).reshape((comps_y * n, ncols), order='F') * complex(alpha)
+        if beta != 0:
+            out = out + complex(beta) * y.to_host().reshape((comps_y * n, ncols), order='F')
+        y.copy_from(np.asfortranarray(out.astype(_C64).reshape(y.shape, order='F')))
+
+    def tgv_adjoint(self, gx, gv, p, q, dims):
+        """K^H (p; q) of K (x; v) = (D x - v; E v), column by column: gx += D^H p (gx: N rows per column, read and written) and
+        gv = E^H q - p (gv: 3N rows, written and not read); p has 3N rows, q 6N (`grad3`, `symgrad3`).  Host form in float64
+        through to_host / copy_from; device backends override it."""
+        dims = tuple(int(n) for n in dims)
+        n = int(np.prod(dims))
+        assert gx.size % n == 0 and gv.size == 3 * gx.size and p.size == 3 * gx.size and q.size == 6 * gx.size, \
+            (gx.shape, gv.shape, p.shape, q.shape, dims)
+        ncols = gx.size // n
+        ph = p.to_host().reshape(dims + (3, ncols), order='F').astype(np.complex128)
+        qh = q.to_host().reshape(dims + (6, ncols), order='F').astype(np.complex128)
+        out_x = gx.to_host().reshape((n, ncols), order='F') + _grad_adjoint(ph).reshape((n, ncols), order='F')
+        out_v = _symgrad_adjoint(qh) - ph
+        gx.copy_from(np.asfortranarray(out_x.astype(_C64).reshape(gx.shape, order='F')))
+        gv.copy_from(np.asfortranarray(out_v.astype(_C64).reshape(gv.shape, order='F')))
+
+    def tgv_dual_step(self, p, q, xn, xo, vn, vo, sigma, a1, a0, dims):
+        """The dual step of second-order total generalized variation in place on p and q, column by column, with w_x = 2*xn - xo
+        and w_v = 2*vn - vo:  p <- proj_{a1}(p + sigma (D w_x - w_v)),  q <- proj_{a0}(q + sigma E w_v).  proj_r scales the
+        components at a voxel (three of p, six of q) by (norm <= r ? 1 : r / norm), norm their 2-norm.  Host form in float64
+        through to_host / copy_from; device backends override it."""
+        dims = tuple(int(n) for n in dims)
+        n = int(np.prod(dims))
+        assert xn.size % n == 0 and xo.size == xn.size and vn.size == 3 * xn.size and vo.size == vn.size and p.size == vn.size \
+            and q.size == 6 * xn.size and a1 >= 0 and a0 >= 0, (p.shape, q.shape, xn.shape, xo.shape, vn.shape, vo.shape, dims, a1, a0)
+        ncols = xn.size // n
+        wx = (2.0 * xn.to_host().astype(np.complex128) - xo.to_host().astype(np.complex128)).reshape(dims + (ncols,), order='F')
+        wv = (2.0 * vn.to_host().astype(np.complex128) - vo.to_host().astype(np.complex128)).reshape(dims + (3, ncols), order='F')
+        tp = p.to_host().reshape(dims + (3, ncols), order='F').astype(np.complex128) + float(sigma) * (_grad_forward(wx) - wv)
+        tq = q.to_host().reshape(dims + (6, ncols), order='F').astype(np.complex128) + float(sigma) * _symgrad_forward(wv)
+        p.copy_from(np.asfortranarray(_ball(tp, a1).astype(_C64).reshape(p.shape, order='F')))
+        q.copy_from(np.asfortranarray(_ball(tq, a0).astype(_C64).reshape(q.shape, order='F')))
 
     @staticmethod
     def _llr_block_ids(dims, block, shift):

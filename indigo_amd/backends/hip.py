@@ -883,6 +883,48 @@ class HipBackend(Backend):
         """Backend.tv4_dual_step on the device (ig_tv4_dual_c64), in place on u"""
         self._tv_dual(u, xn, xo, sigma, (mu, mu_t), dims, int(frames))
 
+    def symgrad3(self, y, v, dims, adjoint=False, alpha=1, beta=0):
+        """Backend.symgrad3 on the device (ig_symgrad3_c64 / ig_symgrad3h_c64): panels of any column count with their leading
+        dimensions, or the columns stacked in one vector"""
+        assert v.dtype == _C64 and y.dtype == _C64, "only complex64 is supported"
+        n0, n1, n2 = (int(n) for n in dims)
+        n = n0 * n1 * n2
+        rows_v, rows_y = (6 * n, 3 * n) if adjoint else (3 * n, 6 * n)
+        assert n > 0 and v.size % rows_v == 0 and v.size // rows_v * rows_y == y.size, (v.shape, y.shape, dims)
+        ncols = v.size // rows_v
+        (vp, ldv), (yp, ldy) = self._frame_panel(v, rows_v, ncols), self._frame_panel(y, rows_y, ncols)
+        ar, ai = _cplx(alpha)
+        br, bi = _cplx(beta)
+        name = "ig_symgrad3%s_c64" % ("h" if adjoint else "")
+        self._check(getattr(self._L, name)(self._ctx, n0, n1, n2, ncols, vp, ldv, ar, ai, br, bi, yp, ldy), name)
+
+    def _tgv_panels(self, dims, first, *rest):
+        """(n0, n1, n2, ncols) and the (pointer, leading dimension) pairs of complex64 panels given as (array, rows / N): the column
+        count is that of the first"""
+        n0, n1, n2 = (int(n) for n in dims)
+        n = n0 * n1 * n2
+        assert n > 0 and first[0].size % (first[1] * n) == 0, (first[0].shape, dims)
+        ncols = first[0].size // (first[1] * n)
+        flat = []
+        for a, comps in (first,) + rest:
+            assert a.dtype == _C64, "only complex64 is supported"
+            assert a.size == comps * n * ncols, (a.shape, comps, dims, ncols)
+            flat.extend(self._frame_panel(a, comps * n, ncols))
+        return (n0, n1, n2, ncols), flat
+
+    def tgv_adjoint(self, gx, gv, p, q, dims):
+        """Backend.tgv_adjoint on the device (ig_tgv_kh_c64): gx += D^H p and gv = E^H q - p in one pass"""
+        head, panels = self._tgv_panels(dims, (p, 3), (q, 6), (gx, 1), (gv, 3))
+        self._check(self._L.ig_tgv_kh_c64(self._ctx, *head, *panels), "ig_tgv_kh_c64")
+
+    def tgv_dual_step(self, p, q, xn, xo, vn, vo, sigma, a1, a0, dims):
+        """Backend.tgv_dual_step on the device (ig_tgv_dual_c64), in place on p and q"""
+        head, ins = self._tgv_panels(dims, (xn, 1), (xo, 1), (vn, 3), (vo, 3))
+        same, outs = self._tgv_panels(dims, (p, 3), (q, 6))
+        assert same == head, (p.shape, xn.shape, dims)
+        self._check(self._L.ig_tgv_dual_c64(self._ctx, *head, *ins, ctypes.c_float(float(sigma)), ctypes.c_float(float(a1)),
+                                            ctypes.c_float(float(a0)), *outs), "ig_tgv_dual_c64")
+
     def _llr_args(self, x, dims, frames, block, shift):
         """the leading arguments of ig_llr_svt_c64 / ig_llr_nuc_c64, the panel pointer and its leading dimension, and nb"""
         assert x.dtype == _C64, "only complex64 is supported"

@@ -802,6 +802,30 @@ class Gradient(MatrixFreeOperator):
         self._backend.grad3(y, x, self._dims, adjoint=not forward, alpha=alpha, beta=beta)
 
 
+class SymGradient(MatrixFreeOperator):
+    """The symmetrised backward difference E of a 3-component complex64 field on an F-ordered volume of shape `dims` with N voxels,
+    shape (6N, 3N): component a of the input in rows [aN, (a+1)N), the components xx, yy, zz, xy, xz, yz of the output in rows
+    [cN, (c+1)N).  With B_a = -D_a^H the backward difference that matches `Gradient`: (E v)_aa = B_a v_a and (E v)_ab = (B_b v_a +
+    B_a v_b) / sqrt(2), stored once, so that the 2-norm of the six is the Frobenius norm of the symmetric tensor.  .H is the adjoint;
+    ||E||^2 <= 12.  The second analysis operator of pics --tgv."""
+
+    def __init__(self, backend, dims, **kwargs):
+        self._dims = tuple(int(n) for n in dims)
+        if len(self._dims) != 3 or min(self._dims) < 1:
+            raise ValueError("SymGradient: dims must be three positive lengths, got %s" % (dims,))
+        n = int(np.prod(self._dims))
+        kwargs.setdefault('name', 'symgradient')
+        super().__init__(backend, shape=(6 * n, 3 * n), **kwargs)
+
+    def _eval(self, y, x, alpha=1, beta=0, forward=True, left=True):
+        trace = getattr(self._backend, 'trace', None)
+        if trace is not None:
+            # either way three components and six move (72 B per voxel); beta != 0 reads the output as well
+            trace.add('symgradient', nbytes=72 * (self.shape[1] // 3) * x.shape[1] + (0 if beta == 0 else y.nbytes), nflops=0,
+                      shape=x.shape, forward=forward, name=self._name)
+        self._backend.symgrad3(y, x, self._dims, adjoint=not forward, alpha=alpha, beta=beta)
+
+
 class GradientT(MatrixFreeOperator):
     """The gradient D4 of T = `frames` time frames of an F-ordered complex64 volume of shape `dims` with N voxels, shape (4NT, NT).
     The input is frame-major, frame t in rows [tN, (t+1)N); the output holds 4N rows per frame: components 0..2 are `Gradient`'s

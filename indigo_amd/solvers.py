@@ -1,6 +1,6 @@
 """The proximal solvers of the reconstruction drivers and what they are made of: the power iteration that sizes their steps, the
 non-smooth terms with their proximal maps (`ProxTerm`: L1-wavelet, locally low rank), the smooth data term that both solvers share,
-and the solvers themselves, `fista_solve` and `tv_solve`, on top of `Backend.fista` and `Backend.primal_dual`.  They log as `pics`,
+and the solvers themselves, `fista_solve`, `tv_solve` and `tgv_solve`, on top of `Backend.fista` and `Backend.primal_dual`.  They log as `pics`,
 the driver they serve (`indigo_amd.pics`; nlinv and ecalib take the power iteration)."""
 import collections
 import logging
@@ -199,3 +199,77 @@ def tv_solve(B, AHA, AHy, dims, iters, mu, sigma=None, l1=0.0, wavelet='db2', le
     x = np.zeros((n, 1), dtype=_C64, order='F')
     B.primal_dual(gradf, term.proxg if term is not None else None, KH, dual_step, tau, x, u, maxiter=iters, callback=callback)
     return x, objectives
+
+
+def tgv_solve(B, AHA, AHy, dims, iters, a1, a0, sigma=None, l1=0.0, wavelet='db2', levels=3, power_iters=15, step=None, ynorm2=0.0,
+              frames=1, term=None):
+    """min_{x, v} 1/2 x^H AHA x - Re(x^H AHy) + ynorm2 / 2 + a1 sum_i ||(D x - v)_i||_2 + a0 sum_i ||(E v)_i||_F [+ l1 ||W x||_1]
+    by Backend.primal_dual from zero: second-order total generalized variation (Bredies, Kunisch, Pock 2010).  D is
+    operators.Gradient, E operators.SymGradient, v a 3-component field that takes up the smooth part of the differences of x.  With
+    K (x; v) = (D x - v; E v):  K^H is Backend.tgv_adjoint, the dual step Backend.tgv_dual_step, the projections of p onto the
+    2-norm ball of radius a1 over 3 components and of q onto that of radius a0 over 6, at every voxel.  proxg acts on the x rows
+    only: `wavelet_prox` when l1 > 0, that of `term` (`llr_term`) when one is given, else the identity.
+
+    Layout, n = N * frames: the primal vector has 4n rows, x in [0, n) and v in [n, 4n) as a 3N x frames panel; the dual has 9n rows,
+    p a 3N x frames panel in [0, 3n) and q a 6N x frames panel in [3n, 9n).  The frames (time frames, sets of maps or coefficient
+    images) are independent columns: every image has its own v.  gradf evaluates AHA on the x rows and leaves the v rows to K^H,
+    which writes them.
+
+    Steps: L and tau = 0.9 / L as in `tv_solve`; sigma = L / 32 unless given.  With ||K||^2 <= 16:  1/tau - 16 sigma = L/0.9 - L/2,
+    the margin that `tv_solve` keeps.
+    Returns the image as a host (n, 1) array and the objectives logged: [(iteration, value)], every 10 iterations and the last."""
+    cols = int(frames)
+    N = int(np.prod(dims))
+    n = AHA.shape[1]
+    assert n == N * cols, (AHA.shape, dims, frames)
+    L, _ = choose_step(B, AHA, power_iters, step, "tgv", False)
+    tau = 0.9 / L
+    if sigma is None:
+        sigma = L / 32
+    log.info("tgv: tau %.6e, sigma %.6e, a1 %g, a0 %g, %s", tau, sigma, a1, a0, tuple(dims))
+    if cols > 1:
+        log.info("tgv: %d images, each with its own v", cols)
+    assert term is None or not l1 > 0, "one prox slot: the wavelet term or `term`"
+    if l1 > 0:
+        term = wavelet_term(B, dims, l1, wavelet, levels)
+    if term is not None:
+        log.info("tgv: %s", term.text)
+    G, E = B.Gradient(dims), B.SymGradient(dims)
+    work, last = {}, {}
+
+    def objective(val, x):
+        if not work:
+            work['d'] = B.zero_array((3 * n, 1), _C64, name='objective.d')
+            work['e'] = B.zero_array((6 * n, 1), _C64, name='objective.e')
+        v = last['z'].dense_rows(n, 4 * n)
+        G.eval(work['d'].reshape((3 * N, cols)), x.reshape((N, cols)))
+        B.axpby(1, work['d'], -1, v)                                   # D x - v
+        E.eval(work['e'].reshape((6 * N, cols)), v.reshape((3 * N, cols)))
+        for radius, name, comps in ((a1, 'd', 3), (a0, 'e', 6)):
+            t = work[name].to_host().reshape((N, comps, cols), order='F').astype(np.complex128)
+            val += radius * float(np.sqrt((np.abs(t) ** 2).sum(axis=1)).sum())
+        return val if term is None else val + term.value(x)
+
+    gradf_x, callback_x, objectives = smooth_term(B, AHA, AHy, ynorm2, "tgv", iters, objective)
+
+    def gradf(g, z):
+        gradf_x(g.dense_rows(0, n), z.dense_rows(0, n))
+
+    def KH(g, u):
+        B.tgv_adjoint(g.dense_rows(0, n), g.dense_rows(n, 4 * n), u.dense_rows(0, 3 * n), u.dense_rows(3 * n, 9 * n), dims)
+
+    def proxg(g, t):
+        term.proxg(g.dense_rows(0, n), t)
+
+    def dual_step(u, zn, zo):
+        B.tgv_dual_step(u.dense_rows(0, 3 * n), u.dense_rows(3 * n, 9 * n), zn.dense_rows(0, n), zo.dense_rows(0, n),
+                        zn.dense_rows(n, 4 * n), zo.dense_rows(n, 4 * n), sigma, a1, a0, dims)
+
+    def callback(k, z):
+        last['z'] = z
+        callback_x(k, z.dense_rows(0, n))
+
+    u = B.zero_array((9 * n, 1), _C64, name='tgv.u')
+    z = np.zeros((4 * n, 1), dtype=_C64, order='F')
+    B.primal_dual(gradf, proxg if term is not None else None, KH, dual_step, tau, z, u, maxiter=iters, callback=callback)
+    return np.asfortranarray(z[:n]), objectives
