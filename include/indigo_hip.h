@@ -310,6 +310,29 @@ int  ig_fmap_phase_c64(ig_ctx* ctx, int64_t n, int64_t L, const float* f, double
 int  ig_fmap_combine_c64(ig_ctx* ctx, int64_t n, int64_t L, int64_t P, const void* b, int64_t ldb, int adjoint,
                          const void* x, int64_t ldx, float alpha_re, float alpha_im, float beta_re, float beta_im,
                          void* y, int64_t ldy);
+/* Field-map estimation from E echo images, the map that pics --fmap takes (Backend.fieldmap_init / fieldmap_step, python -m
+ * indigo_amd.fmapest).  No counterpart in the reference; bart/MIRT `mri_field_map_reg`: the penalised-likelihood
+ * fit of Funai et al. (IEEE TMI 27:1484, 2008) by separable quadratic surrogates.  y is the N x E complex64 panel of the echo
+ * images on the F-ordered n0 x n1 x n2 volume of N voxels (device, column-major, ldy >= N in elements), y_l ~ m exp(-2 pi i f
+ * te_l); f, f_old, f_new are device arrays of N float32 values in Hz.  For the pairs l < m, in the order (0,1), (0,2), ..,
+ * (0,E-1), (1,2), ..:  p = y_m conj(y_l), w = |p|, k = 2 pi (te_m - te_l), s = pv(arg p + k f) in [-pi, pi]:
+ *   Psi(f) = sum_j sum_pairs w (1 - cos s)  +  beta / 2 sum_edges (f_j - f_j')^2     (edges: nearest neighbours along the three axes,
+ *                                                                                    no wrap-around: the forward differences of ig_grad3_c64)
+ *   g_j = sum_pairs w k sin s + beta sum_{j' ~ j} (f_j - f_j'),   d_j = sum_pairs w k^2 sin(s) / s + 2 beta deg_j   (sin(0) / 0 = 1)
+ * ig_fmapest_init_r32:  f[j] = -arg(y_1 conj(y_0))[j] / (2 pi (te1 - te0)); no unwrapping: the true field has to satisfy
+ *   |f| < 1 / (2 (te1 - te0)).  Reads the first two columns of y.
+ * ig_fmapest_step_r32:  f_new[j] = f_old[j] - g_j / d_j  (d_j == 0: f_new[j] = f_old[j]), every voxel from f_old.  te: E echo
+ *   times in seconds ON THE HOST, strictly increasing; 2 <= E <= 8; beta >= 0 (absolute).  parts != NULL: the same pass also
+ *   writes ig_fmapest_cost_parts(n0, n1, n2) doubles to the device array parts (nparts >= that many), one per workgroup, whose
+ *   sum in index order is Psi(f_old), the cost of the INPUT iterate; accumulated in double in a fixed order, so the same bits
+ *   from call to call, and f_new is the same bits with and without.  f_new == NULL with parts != NULL: the cost alone.  The
+ *   phase (te_m - te_l) f is formed in double and reduced to [-1/2, 1/2] cycles before the float sine and cosine.  f_new must
+ *   overlap neither f_old nor y, parts none of the three; echo times, E, beta or overlap out of these bounds are IG_ERR_ARG,
+ *   with nothing written.  One pass: 8 E + 8 bytes per voxel.                                                                  */
+int64_t ig_fmapest_cost_parts(int64_t n0, int64_t n1, int64_t n2);
+int  ig_fmapest_init_r32(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, const void* y, int64_t ldy, double te0, double te1, float* f);
+int  ig_fmapest_step_r32(ig_ctx* ctx, int64_t n0, int64_t n1, int64_t n2, int64_t E, const void* y, int64_t ldy, const double* te,
+                         float beta, const float* f_old, float* f_new, double* parts, int64_t nparts);
 /* The K x K point-spread mixing pass of the Toeplitz normal operator (operators.ToeplitzNormal, Backend.psf_mix,
  * pics --toeplitz).  No reference counterpart.
  *   y[g, c, k] = sum_k' P[g][k, k'] * x[g, c, k']        g < n grid points, c < nc coils, k < nk

@@ -100,6 +100,10 @@ PROTOTYPES = {
                                    c_float, c_float, c_float, c_float, c_void_p, c_int64]),
     "ig_fmap_combine_c64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64,
                                     c_float, c_float, c_float, c_float, c_void_p, c_int64]),
+    "ig_fmapest_cost_parts": (c_int64, [c_int64, c_int64, c_int64]),
+    "ig_fmapest_init_r32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_double, c_double, c_void_p]),
+    "ig_fmapest_step_r32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_float,
+                                    c_void_p, c_void_p, c_void_p, c_int64]),
     "ig_psf_mix_c64":     (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64]),
     "ig_coil_maps_c64":   (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p,
                                    c_float, c_float, c_float, c_float, c_void_p, c_int64, c_int64, c_int64]),

@@ -969,6 +969,108 @@ class Backend(object):
             out = out + complex(beta) * y.to_host().reshape((n, cols_y), order='F')
         y.copy_from(np.asfortranarray(out.astype(_C64).reshape(y.shape, order='F')))
 
+    @staticmethod
+    def _share_memory(a, b):
+        """whether two backend arrays share a byte: host arrays by numpy's bounds, device arrays by their address ranges"""
+        if isinstance(a._arr, np.ndarray):
+            return bool(np.may_share_memory(a._arr, b._arr))
+
+        def span(v):
+            cols = v.shape[1] if v.ndim == 2 else 1
+            return int(v._arr), int(v._arr) + ((cols - 1) * v._leading_dim + v.shape[0]) * v.itemsize
+        (a0, a1), (b0, b1) = span(a), span(b)
+        return a0 < b1 and b0 < a1
+
+    def fieldmap_check(self, what, dims, y, te, fields, beta=0.0):
+        """The refusals that fieldmap_init and fieldmap_step share, every one a ValueError: returns (dims, N, E, te as float64,
+        beta as what its float32 value says)."""
+        dims = tuple(int(n) for n in dims)
+        te = np.ascontiguousarray(np.asarray(te, dtype=np.float64).reshape(-1))
+        E = te.size
+        if len(dims) != 3 or min(dims) < 1:
+            raise ValueError("%s: dims %r are not three positive lengths" % (what, dims))
+        n = int(np.prod(dims))
+        if not 2 <= E <= 8:
+            raise ValueError("%s: %d echo times, between 2 and 8 echoes are supported" % (what, E))
+        if not (np.isfinite(te).all() and (np.diff(te) > 0).all()):
+            raise ValueError("%s: the echo times %r are not strictly increasing" % (what, te.tolist()))
+        if y.dtype != _C64 or y.size != n * E:
+            raise ValueError("%s: the panel %r of %s is not N x E = %d x %d complex64" % (what, y.shape, y.dtype, n, E))
+        for f in fields:
+            if f.dtype != np.dtype('float32') or f.size != n or not f.contiguous:
+                raise ValueError("%s: a field %r of %s is not N = %d contiguous float32 values" % (what, f.shape, f.dtype, n))
+            if self._share_memory(f, y):
+                raise ValueError("%s: a field overlaps the panel" % what)
+        if len(fields) == 2 and self._share_memory(fields[0], fields[1]):
+            raise ValueError("%s: f_new overlaps f_old" % what)
+        beta = float(beta)
+        if not (np.isfinite(beta) and beta >= 0):
+            raise ValueError("%s: beta %r is negative or not finite" % (what, beta))
+        return dims, n, E, te, float(np.float32(beta))
+
+    def fieldmap_init(self, f, y, dims, te):
+        """f[j] = -angle(y_1 conj(y_0))[j] / (2 pi (te[1] - te[0])), the two-echo phase-difference estimate in Hz that the
+        regularised fit starts from.  y is the N x E complex64 panel of the echo images on the F-ordered `dims`
+        volume, or the same as an (N E, 1) vector, y_l ~ m exp(-2 pi i f te_l) as in pics --fmap; f a backend array of N float32
+        values.  No unwrapping is done: the true field has to satisfy |f| < 1 / (2 (te[1] - te[0])).  Refuses with a ValueError:
+        E outside 2..8, echo times not strictly increasing, a panel whose size is not N E.  Host form in float64 through to_host /
+        copy_from; device backends override it."""
+        dims, n, E, te, _ = self.fieldmap_check("fieldmap_init", dims, y, te, (f,))
+        yh = y.to_host().reshape((n, E), order='F').astype(np.complex128)
+        f0 = -np.angle(yh[:, 1] * yh[:, 0].conj()) / (2.0 * np.pi * (te[1] - te[0]))
+        f.copy_from(np.asfortranarray(f0.astype(np.float32).reshape(f.shape, order='F')))
+
+    def fieldmap_step(self, f_new, f_old, y, te, beta, dims, cost=False):
+        """One separable-quadratic-surrogate step of the penalised-likelihood field-map fit of Funai et al. (IEEE TMI 27:1484,
+        2008), every voxel from the old iterate.  For the echo pairs l < m with p = y_m conj(y_l), w = |p|,
+        k = 2 pi (te_m - te_l) and s the principal value of angle(p) + k f_old in [-pi, pi]:
+            g_j = sum_pairs w k sin s + beta sum_{j' ~ j} (f_j - f_j'),    d_j = sum_pairs w k^2 sin(s) / s + 2 beta deg_j,
+            f_new[j] = f_old[j] - g_j / d_j        (d_j = 0: unchanged)
+        over the nearest neighbours j' along the three axes of the F-ordered `dims` volume, no wrap-around.  It decreases
+            Psi(f) = sum_j sum_pairs w (1 - cos s) + beta / 2 sum_edges (f_j - f_j')^2
+        monotonically; cost=True returns Psi(f_old), the cost of the INPUT iterate, as a float (else None).  beta is absolute and is
+        what its float32 value says.  y as in `fieldmap_init`; f_new and f_old are backend arrays of N float32 values in Hz.  Refuses
+        with a ValueError: E outside 2..8, echo times not strictly increasing, overlapping f_new / f_old, a panel whose size is
+        not N E, beta < 0.  Host form in float64 through to_host / copy_from; device backends override it."""
+        dims, n, E, te, beta = self.fieldmap_check("fieldmap_step", dims, y, te, (f_new, f_old), beta)
+        out, psi = self._fieldmap_host(f_old, y, te, beta, dims, n, E)
+        f_new.copy_from(np.asfortranarray(out.astype(np.float32).reshape(f_new.shape, order='F')))
+        return psi if cost else None
+
+    def fieldmap_cost(self, f, y, te, beta, dims):
+        """Psi(f) of `fieldmap_step` as a float, f untouched: what a step with cost=True returns, without the step.  The same
+        refusals.  Host form in float64; device backends override it."""
+        dims, n, E, te, beta = self.fieldmap_check("fieldmap_cost", dims, y, te, (f,), beta)
+        return self._fieldmap_host(f, y, te, beta, dims, n, E)[1]
+
+    @staticmethod
+    def _fieldmap_host(f_old, y, te, beta, dims, n, E):
+        """(the stepped field as a float64 `dims` array, Psi(f_old)) of the checked arguments of `fieldmap_step`"""
+        yh = y.to_host().reshape((n, E), order='F').astype(np.complex128)
+        f = f_old.to_host().reshape(dims, order='F').astype(np.float64)
+        g, d, psi = np.zeros(dims), np.zeros(dims), 0.0
+        for l in range(E):
+            for m in range(l + 1, E):
+                p = (yh[:, m] * yh[:, l].conj()).reshape(dims, order='F')
+                k = 2.0 * np.pi * (te[m] - te[l])
+                r = p * np.exp(1j * k * f)
+                w, s = np.abs(p), np.angle(r)
+                with np.errstate(divide='ignore', invalid='ignore'):
+                    g += k * r.imag
+                    d += k * k * np.where(s != 0, r.imag / s, w)
+                psi += float((w - r.real).sum())
+        for a in range(3):
+            df = -_fwd_diff(f, a)                             # f_j - f_j' towards the far neighbour, 0 on the far face
+            g += beta * df
+            g -= beta * np.roll(df, 1, axis=a)                # (df is 0 on the far face, so nothing wraps)
+            deg = np.full(dims[a], 2.0 if dims[a] > 1 else 0.0)
+            if dims[a] > 1:
+                deg[0] = deg[-1] = 1.0
+            d += 2.0 * beta * deg.reshape([-1 if b == a else 1 for b in range(3)])
+            psi += 0.5 * beta * float((df ** 2).sum())
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return np.where(d > 0, f - g / d, f), psi
+
     def coil_maps(self, y, x, maps, n, ncoils, nmaps, adjoint=False, alpha=1, beta=0, interleaved=False, width=None):
         """y = beta*y + alpha * S x (adjoint: S^H x), the per-voxel coil-map product of soft-SENSE between M = `nmaps` images and
         C = `ncoils` coil images of `n` voxels:  forward y[i, c] = sum_m S[i, c, m] x[i, m], adjoint

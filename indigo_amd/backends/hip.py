@@ -992,6 +992,44 @@ class HipBackend(Backend):
         self._check(self._L.ig_fmap_combine_c64(self._ctx, n, L, P, ctypes.c_void_p(b._arr), b._leading_dim, int(bool(adjoint)),
                                                 xp, ldx, ar, ai, br, bi, yp, ldy), "ig_fmap_combine_c64")
 
+    def fieldmap_init(self, f, y, dims, te):
+        """Backend.fieldmap_init on the device (ig_fmapest_init_r32): the echo images are the columns of a panel with its leading
+        dimension, or stacked in one column"""
+        dims, n, E, te, _ = self.fieldmap_check("fieldmap_init", dims, y, te, (f,))
+        yp, ldy = self._frame_panel(y, n, E)
+        self._check(self._L.ig_fmapest_init_r32(self._ctx, *dims, yp, ldy, ctypes.c_double(te[0]), ctypes.c_double(te[1]),
+                                                ctypes.c_void_p(f._arr)), "ig_fmapest_init_r32")
+
+    def fieldmap_step(self, f_new, f_old, y, te, beta, dims, cost=False):
+        """Backend.fieldmap_step on the device (ig_fmapest_step_r32).  cost=True: the same pass writes one double per workgroup,
+        which come back and are added here in index order"""
+        dims, n, E, te, beta = self.fieldmap_check("fieldmap_step", dims, y, te, (f_new, f_old), beta)
+        return self._fieldmap_launch(f_new, f_old, y, te, beta, dims, n, E, cost)
+
+    def fieldmap_cost(self, f, y, te, beta, dims):
+        """Backend.fieldmap_cost on the device (ig_fmapest_step_r32 without f_new: the cost alone)"""
+        dims, n, E, te, beta = self.fieldmap_check("fieldmap_cost", dims, y, te, (f,), beta)
+        return self._fieldmap_launch(None, f, y, te, beta, dims, n, E, True)
+
+    def _fieldmap_launch(self, f_new, f_old, y, te, beta, dims, n, E, cost):
+        yp, ldy = self._frame_panel(y, n, E)
+        parts, nparts = None, 0
+        if cost:
+            nparts = int(self._L.ig_fmapest_cost_parts(*dims))
+            parts = getattr(self, '_fmapest_parts', None)
+            if parts is None or parts.size < nparts:
+                parts = self._fmapest_parts = self.empty_array((nparts,), np.dtype('float64'), name='fmapest.parts')
+        self._check(self._L.ig_fmapest_step_r32(self._ctx, *dims, E, yp, ldy, ctypes.c_void_p(te.ctypes.data), ctypes.c_float(beta),
+                                                ctypes.c_void_p(f_old._arr), ctypes.c_void_p(f_new._arr) if f_new is not None else None,
+                                                ctypes.c_void_p(parts._arr) if cost else None, parts.size if cost else 0),
+                    "ig_fmapest_step_r32")
+        if not cost:
+            return None
+        total = 0.0
+        for v in parts.to_host().reshape(-1)[:nparts].tolist():     # a fixed order: the same bits from call to call
+            total += v
+        return total
+
     def coil_maps(self, y, x, maps, n, ncoils, nmaps, adjoint=False, alpha=1, beta=0, interleaved=False, width=None):
         """Backend.coil_maps on the device (ig_coil_maps_c64): the images and the coil-major coil images are the columns of panels
         with their leading dimensions, or stacked in one column; interleaved coil images are one contiguous array"""

@@ -19,7 +19,7 @@ OBJDIR = os.path.join(HERE, "lib", "obj")
 LIBNAME = "libindigo_hip.so"
 
 SOURCES = ["ig_fft_abd0.hip", "ig_fft_abd1.hip", "ig_fft_abd2.hip", "ig_fft_abd3.hip", "ig_fft.hip", "ig_spmm.hip", "ig_fft_plain.hip", "ig_fft_plan.hip", "ig_spmm_bricks.hip", "ig_spmm_runs.hip", "ig_gridsep.hip", "ig_context.hip", "ig_blas.hip",
-           "ig_permute.hip", "ig_wavelet.hip", "ig_tv.hip", "ig_tgv.hip", "ig_llr.hip", "ig_basis.hip", "ig_fmap.hip", "ig_toep.hip", "ig_maps.hip", "ig_nlinv.hip", "ig_espirit.hip", "ig_cc.hip", "ig_dict.hip", "ig_epg.hip", "ig_dcf.hip", "ig_comm.hip", "ig_interp.hip", "ig_dense.hip"]       # (the slow ones first: four compile side by side)
+           "ig_permute.hip", "ig_wavelet.hip", "ig_tv.hip", "ig_tgv.hip", "ig_llr.hip", "ig_basis.hip", "ig_fmap.hip", "ig_fmapest.hip", "ig_toep.hip", "ig_maps.hip", "ig_nlinv.hip", "ig_espirit.hip", "ig_cc.hip", "ig_dict.hip", "ig_epg.hip", "ig_dcf.hip", "ig_comm.hip", "ig_interp.hip", "ig_dense.hip"]       # (the slow ones first: four compile side by side)
 ARCH = "gfx950"
 CXXFLAGS = [
     "--offload-arch=%s" % ARCH, "-O3", "-std=c++17", "-fPIC",
